@@ -12,11 +12,24 @@ per-shard skew (1.5 % at 8 shards) cancels -- and a rank packs N batches into on
 (a launch holds up to 262144 integrals: N x 32768 shards of 1/N each, the work of one GPU's
 32768-integral launch, whatever N <= 8). The partial results of the K timed steps are combined with
 ONE all-reduce inside the timed region. Launches are pipelined
-(no host sync between them); every integral's counts are verified bit-exactly and its area to
-1e-12 relative against the golden tree after timing.
+(no host sync between them).
 
-After the headline's timed region, four secondary passes are timed the same way (barrier + sync on
-both sides, max over ranks) and reported under "secondary":
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the last
+step's results where --dump-outputs asks for them, print the line. It fails (exit 3) only where an
+integral reports an error. Everything else runs with --full: the CPU baseline before any GPU call,
+the one-integral-per-launch latency probe, the check of every timed integral against the golden tree
+(counts bit-exact, area to 1e-12 relative; the per-CU task counters against the tasks) and the
+secondary passes below. Without --full the line's cpu_baseline, single_integral_kernel_us,
+tasks_per_cu, secondary and verified are null, and checks holds the error flags alone.
+
+--dump-outputs DIR writes what the last timed step returned to its caller -- one row per integral of
+the batch, after the all-reduce -- as DIR/area.npy, DIR/tasks.npy, DIR/accepted.npy and
+DIR/errors.npy (float64, B values each: 1 MiB in all at the default batch). The inputs are fixed
+(every integral is cosh4 on [0,5] at --eps), so two builds run with the same arguments can be
+compared array for array.
+
+With --full, after the headline's timed region, four secondary passes are timed the same way
+(barrier + sync on both sides, max over ranks) and reported under "secondary":
   * C3 (BASELINE configs[2]): 1 000 000 splitmix64-bounded integrals at EPSILON=1e-10, split into
     contiguous whole-integral blocks per rank, through the batch front end (aq_integrate_batch);
     verified by T = 2L - 1 for every integral, the committed per-integral prefix and the exact KAT
@@ -29,12 +42,13 @@ both sides, max over ranks) and reported under "secondary":
   * C3 again at EPSILON=1e-3 (SURVEY §8d's launch/compaction-bound run: ~1 400 tasks per integral),
     verified the same way (the first 256 integrals, the 10 000-draw KAT: mean leaves 711.4936).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eps E] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eps E] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-single] [--no-secondary] [--c3-n M]]
 
---gpus N > 1 with no launcher (WORLD_SIZE unset): this process times the CPU baseline first (no GPU
-call), then runs N ranks itself through `torch.distributed.run` and exits with their status. Under a
-launcher WORLD_SIZE must equal --gpus (aquadPartA.c:86-90: the process count is the launch's, and a
-mismatch is an error, not a fallback).
+--gpus N > 1 with no launcher (WORLD_SIZE unset): this process times the CPU baseline first (--full
+only; no GPU call), then runs N ranks itself through `torch.distributed.run` and exits with their
+status. Under a launcher WORLD_SIZE must equal --gpus (aquadPartA.c:86-90: the process count is the
+launch's, and a mismatch is an error, not a fallback).
 
 Prints ONE JSON line (rank 0). `value` = accepted subintervals/s over all GPUs; roofline is the
 persistent kernel's FP64 rate (38 algorithmic FLOP per task) over its HIP-event
@@ -191,6 +205,15 @@ def splitmix64_bounds(n):
     return np.minimum(a, b), np.maximum(a, b)
 
 
+def dump_outputs(path, rows):
+    """--dump-outputs: the last timed step's results as the caller receives them, one (area, tasks,
+    accepted, error) row per integral of the batch, a float64 array per column."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for col, name in enumerate(("area", "tasks", "accepted", "errors")):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(rows[:, col], dtype=np.float64))
+
+
 def ubench_step2():
     """The two-pairs-per-lane microbenchmark of the kernel's per-pair arithmetic (profiles/ceiling.json,
     tools/ubench_step2.hip), or None. It is NOT a bound on the kernel: its loop issues 76 FP64 + 33
@@ -324,8 +347,8 @@ def launcher_cmd(n, argv, port):
 
 
 def spawn_ranks(args, argv, runner=None, baseline=cpu_baseline):
-    """--gpus N > 1 without a launcher: time the CPU baseline here (this process makes no GPU call),
-    run N ranks as a child `torch.distributed.run`, hand the baseline to rank 0 through the
+    """--gpus N > 1 without a launcher: with --full time the CPU baseline here (this process makes no
+    GPU call), run N ranks as a child `torch.distributed.run`, hand the baseline to rank 0 through the
     environment, and return the children's exit status (non-zero if any rank failed)."""
     env = dict(os.environ)
     # RCCL's intra-node transport and torch's CUDA-tensor sharing use HIP IPC handles; this host
@@ -333,7 +356,7 @@ def spawn_ranks(args, argv, runner=None, baseline=cpu_baseline):
     # cross-process handle fails (`hipIpcGetMemHandle: invalid argument`). The GPU pool exports it;
     # the ranks get it explicitly, before any GPU call, whatever the parent's environment
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         env[CPU_ENV] = json.dumps(baseline(args.eps))
     runner = runner or (lambda cmd, env: subprocess.call(cmd, env=env))
     return runner(launcher_cmd(args.gpus, argv, free_port()), env)
@@ -348,10 +371,17 @@ def parse(argv):
                     help="integrals per step (one persistent launch per step on one GPU: ~0.5 ms of ramp-up and "
                          "end-of-launch tail per launch, 2 %% of an 8192-integral launch, 0.5 %% of 32768)")
     ap.add_argument("--eps", type=float, default=1e-10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (one row per integral) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline, the one-integral latency probe and the secondary passes, and "
+                         "check every timed integral against the golden tree (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-single", action="store_true",
-                    help="skip the one-integral-per-launch latency probe (profiling runs: every dispatch is K-wide)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C5 passes after the headline")
+                    help="with --full: skip the one-integral-per-launch latency probe (profiling runs: every "
+                         "dispatch is K-wide)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the C3 / C5 / C4 passes after the headline")
     ap.add_argument("--c3-n", type=int, default=C3_N, help="integrals of the C3 pass")
     return ap.parse_args(argv)
 
@@ -361,6 +391,8 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -376,7 +408,7 @@ def main(argv=None):
     # CPU baseline first: before this process touches the GPU (child processes only). Handed over by
     # this script's own launcher, else timed by rank 0 here (the other ranks wait in the rendezvous).
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = json.loads(os.environ[CPU_ENV]) if os.environ.get(CPU_ENV) else cpu_baseline(args.eps)
 
     import numpy as np
@@ -455,7 +487,7 @@ def main(argv=None):
     # the kernel of the synchronous call a user makes for one integral (aq_integrate: its result slot
     # is re-zeroed by the fetch, so nothing is enqueued before the launch), on N the rank's shard
     single_ms, single_n = 0.0, 0
-    if not args.no_single:
+    if args.full and not args.no_single:
         one = (lambda: ctx.integrate(Problem(eps=args.eps))) if world == 1 else (lambda: launch(1))
         one()                         # untimed: the first K=1 launch pays the K=1 setup
         ctx.synchronize()
@@ -471,7 +503,8 @@ def main(argv=None):
         launch(m * B)
     ctx.synchronize()
 
-    ctx.cu_task_counters(reset=True)   # per-CU task counters over the timed launches only
+    if args.full:
+        ctx.cu_task_counters(reset=True)   # per-CU task counters over the timed launches only
     K = args.steps
     n_int = K * B
     totals = torch.zeros((n_int, 4), dtype=torch.float64, device="cuda")
@@ -510,18 +543,24 @@ def main(argv=None):
     per_launch = n_int / max(launches, 1)
 
     # this rank's tasks per CU over the timed launches (every launch shape keeps them: aq_cu_task_counters)
-    cu = ctx.cu_task_counters(reset=True)
-    cu_v = list(cu.values())
-    cu_stats = {"n_cu": len(cu_v), "min": min(cu_v) if cu_v else 0, "max": max(cu_v) if cu_v else 0,
-                "imbalance": (max(cu_v) * len(cu_v) / sum(cu_v)) if cu_v and sum(cu_v) else None,
-                "sum": sum(cu_v)}
+    cu_stats = None
+    if args.full:
+        cu = ctx.cu_task_counters(reset=True)
+        cu_v = list(cu.values())
+        cu_stats = {"n_cu": len(cu_v), "min": min(cu_v) if cu_v else 0, "max": max(cu_v) if cu_v else 0,
+                    "imbalance": (max(cu_v) * len(cu_v) / sum(cu_v)) if cu_v and sum(cu_v) else None,
+                    "sum": sum(cu_v)}
 
-    # verify every timed step against the golden tree: counts exact, areas to AREA_RTOL
+    # the timed steps' results: no integral may report an error; with --full every one is verified
+    # against the golden tree as well, counts exact and areas to AREA_RTOL
     tot = totals.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tot[(K - 1) * B:])
+    checks = {"errors": bool((tot[:, 3] == 0).all()), "ranks": seen == world}
     tg, lg, ag = GOLDEN.get(args.eps, (None, None, None))
-    checks = {"errors": bool((tot[:, 3] == 0).all()), "ranks": seen == world,
-              "cu_counters": cu_stats["sum"] == int(my_tasks.item())}
-    if tg is not None:
+    if args.full:
+        checks["cu_counters"] = cu_stats["sum"] == int(my_tasks.item())
+    if args.full and tg is not None:
         checks["counts"] = bool((tot[:, 1] == tg).all() and (tot[:, 2] == lg).all())
         checks["areas"] = areas_ok(tot[:, 0], ag)
     # every rank's view (the per-CU check is per rank)
@@ -536,7 +575,7 @@ def main(argv=None):
     achieved = FLOP_PER_TASK * tasks_per_launch / (kern_avg_ms * 1e-3) if kern_avg_ms > 0 else 0.0
 
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         secondary = [
             c3_pass(ctx, args, rank, world, barrier, in_turn, reduce_list, dist),
             c5_pass(ctx, rank, world, barrier, launch, reduce_list, dist, torch, all_reduce),
@@ -549,9 +588,10 @@ def main(argv=None):
         # the persistent launch's shape behind the roofline: workgroups (waves / 12: 768-thread
         # workgroups), waves and the device's CUs (AQ_GRID can set fewer workgroups than CUs)
         shape = (ctx.num_workers // 12, ctx.num_workers, ctx.num_cus)
+        # `verified` speaks of the golden check: null in a plain run that ran none (false if it failed anyway)
         out = bench_line(args, world, K, B, n_int, elapsed, accepted_total, f_evals, tot, per_launch, shape,
-                         single_ms, single_n, ok, backend, seen, stats, achieved, kern_avg_ms, tasks_per_launch, cpu,
-                         cu_stats, secondary, checks)
+                         single_ms, single_n, ok if args.full or not ok else None, backend, seen, stats, achieved,
+                         kern_avg_ms, tasks_per_launch, cpu, cu_stats, secondary, checks)
         print(json.dumps(out))
     ctx.close()
     if distributed:

@@ -79,14 +79,16 @@ def test_bench_line_single_process():
 
 
 def test_launcher_spawns_n_ranks_after_the_cpu_baseline():
-    """--gpus 2 with no launcher: the CPU baseline is timed first (no GPU call in this process), then
-    ONE child torch.distributed.run starts 2 ranks of this same script with the same arguments, the
-    baseline travels to rank 0 through the environment, and the children's status is returned."""
+    """--gpus 2 --full with no launcher: the CPU baseline is timed first (no GPU call in this process),
+    then ONE child torch.distributed.run starts 2 ranks of this same script with the same arguments, the
+    baseline travels to rank 0 through the environment, and the children's status is returned. A plain
+    run (no --full) times no baseline."""
     import json
     sys.path.insert(0, ROOT)
     import bench
     calls, order = [], []
-    args = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
+    args = bench.parse(argv)
 
     def baseline(eps):
         order.append("baseline")
@@ -97,21 +99,26 @@ def test_launcher_spawns_n_ranks_after_the_cpu_baseline():
         calls.append((cmd, env))
         return 7
 
-    rc = bench.spawn_ranks(args, ["--gpus", "2", "--steps", "3", "--warmup", "1"], runner=runner, baseline=baseline)
+    rc = bench.spawn_ranks(args, argv, runner=runner, baseline=baseline)
     assert rc == 7 and order == ["baseline", "runner"] and len(calls) == 1
     cmd, env = calls[0]
     assert cmd[1:3] == ["-m", "torch.distributed.run"]
     assert "--nproc-per-node=2" in cmd and "--nnodes=1" in cmd and "127.0.0.1" in cmd
-    assert cmd[-7:] == [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    assert cmd[-8:] == [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     assert json.loads(env[bench.CPU_ENV]) == {"value": 1.0, "kind": "port", "eps": 1e-10}
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"   # the dmabuf IPC mode RCCL needs, set for the ranks
     # --no-cpu-baseline: nothing timed, nothing handed over
     calls.clear()
     order.clear()
-    args = bench.parse(["--gpus", "4", "--no-cpu-baseline"])
+    args = bench.parse(["--gpus", "4", "--full", "--no-cpu-baseline"])
     env0 = dict(os.environ)
     env0.pop(bench.CPU_ENV, None)
-    rc = bench.spawn_ranks(args, ["--gpus", "4", "--no-cpu-baseline"], runner=runner, baseline=baseline)
+    rc = bench.spawn_ranks(args, ["--gpus", "4", "--full", "--no-cpu-baseline"], runner=runner, baseline=baseline)
+    assert rc == 7 and order == ["runner"] and bench.CPU_ENV not in calls[0][1]
+    # a plain run: the same
+    calls.clear()
+    order.clear()
+    rc = bench.spawn_ranks(bench.parse(["--gpus", "4"]), ["--gpus", "4"], runner=runner, baseline=baseline)
     assert rc == 7 and order == ["runner"] and bench.CPU_ENV not in calls[0][1]
 
 
@@ -144,6 +151,23 @@ def test_c3_bounds_and_kat_fixture():
     assert g[k3["kat_tasks"]] == 2 * g[k3["kat_leaves"]] - g[k3["kat_n"]]
     assert round(g[k3["kat_leaves"]] / g[k3["kat_n"]], 1) == 711.5
     assert len(g[k3["leaves"]]) == len(g[k3["area_hex"]]) == 256
+
+
+def test_full_is_off_by_default_and_dump_outputs_writes_the_columns(tmp_path):
+    """A plain run asks for none of the extra passes; --dump-outputs writes the last step's rows as
+    one float64 array per column, bit for bit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    args = bench.parse(["--full", "--dump-outputs", str(tmp_path / "out")])
+    assert args.full is True and args.dump_outputs == str(tmp_path / "out")
+    rows = np.array([[7583461.361505481, 1464273.0, 732137.0, 0.0], [0.5, 3.0, 2.0, 1.0]])
+    bench.dump_outputs(args.dump_outputs, rows)
+    assert sorted(os.listdir(args.dump_outputs)) == ["accepted.npy", "area.npy", "errors.npy", "tasks.npy"]
+    for col, name in enumerate(("area", "tasks", "accepted", "errors")):
+        got = np.load(os.path.join(args.dump_outputs, name + ".npy"))
+        assert got.dtype == np.float64 and got.tobytes() == rows[:, col].tobytes()
 
 
 def test_area_check():

@@ -80,9 +80,30 @@ def test_bench_collective_block_under_torchrun():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-           "--steps", "2", "--warmup", "1", "--batch", "512", "--no-cpu-baseline", "--no-single"]
+           "--steps", "2", "--warmup", "1", "--batch", "512", "--full", "--no-cpu-baseline", "--no-single"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
     assert res["verified"] is True and res["n_gpus"] == 1 and res["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path, trees):
+    """A plain bench.py run (no --full) times --steps steps, runs none of the extra passes, and
+    --dump-outputs writes what its last step returned: one row per integral of the batch, equal to
+    the golden tree (counts exact, area to 1e-12)."""
+    out_dir = str(tmp_path / "out")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", "512", "--dump-outputs", out_dir]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0 and res["dtype"] == "f64"
+    assert res["per_rank"]["launches"] == [3]
+    assert res["cpu_baseline"] is None and res["secondary"] is None and res["single_integral_kernel_us"] is None
+    assert res["verified"] is None and res["checks"] == {"errors": True, "ranks": True}
+    g = trees["cosh4_eps1e-10"]
+    got = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in ("area", "tasks", "accepted", "errors")}
+    assert all(v.dtype == np.float64 and v.shape == (512,) for v in got.values())
+    assert (got["tasks"] == g["tasks"]).all() and (got["accepted"] == g["leaves"]).all() and (got["errors"] == 0).all()
+    assert np.all(np.abs(got["area"] - float(g["area_quad"])) <= 1e-12 * float(g["area_quad"]))

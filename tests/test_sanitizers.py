@@ -7,6 +7,7 @@ shared-memory protocol on the CPU side. Every run must exit 0 with no sanitizer 
 the golden counts the reference binary pinned (tests/golden/), so a sanitizer build that changed
 the arithmetic would fail too."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -27,8 +28,20 @@ def san():
     return SAN
 
 
+def _fixed_layout():
+    """Command prefix that runs a program without address-space randomisation, where the host allows it:
+    ThreadSanitizer's shadow needs the layout it was built for and ends with "unexpected memory mapping"
+    on kernels that randomise more bits of mmap addresses."""
+    pre = ["setarch", platform.machine(), "-R"]
+    if shutil.which("setarch") and subprocess.run(pre + ["true"], capture_output=True).returncode == 0:
+        return pre
+    return []
+
+
 def _run(args, timeout=120):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", TSAN_OPTIONS="halt_on_error=1")
+    if args[0].endswith("_tsan"):
+        args = _fixed_layout() + args
     r = subprocess.run(args, capture_output=True, text=True, timeout=timeout, env=env)
     for m in REPORT_MARKERS:
         assert m not in r.stderr, r.stderr[-3000:]

@@ -12,8 +12,8 @@ tail -3 "$OUT/gpu_tests.log"
 [ $rc -ne 0 ] && exit $rc
 for step in "$@"; do
   case $step in
-    bench) timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1 ;;
-    bench12) timeout -k 10 400 python bench.py --eps 1e-12 --steps 4 --no-cpu-baseline > "$OUT/bench12.json" 2> "$OUT/bench12.err" || exit 1 ;;
+    bench) timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1 ;;
+    bench12) timeout -k 10 400 python bench.py --full --eps 1e-12 --steps 4 --no-cpu-baseline > "$OUT/bench12.json" 2> "$OUT/bench12.err" || exit 1 ;;
     frontier)
       for w in cosh12 cosh10 sin; do
         timeout -k 10 120 python tools/bench_frontier.py --workload $w --reps 10 > "$OUT/frontier_$w.json" || exit 1

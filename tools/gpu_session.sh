@@ -21,14 +21,14 @@ for step in "$@"; do
     ubench)  run ubench_launch 60 tools/ubench_launch && run ubench_step 120 tools/ubench_step && run ubench_step2 180 tools/ubench_step2 ;;
     ab)      ROUNDS=${ROUNDS:-3} AB_GLOB=${AB_GLOB_K:-libaquad_*.so} run ab 900 bash tools/ab.sh "$TAG" ;;
     front)   AB_GLOB=${AB_GLOB_F:-libaquad_*.so} run front 900 bash tools/frontier_ab.sh "$TAG" ;;
-    bench)   run bench 400 python bench.py ;;
-    bench12) run bench12 400 python bench.py --eps 1e-12 --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline ;;
+    bench)   run bench 400 python bench.py --full ;;
+    bench12) run bench12 400 python bench.py --full --eps 1e-12 --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline ;;
     lone)    run lone 120 python tools/try_single.py ;;
     wall)    run wall 120 python tools/try_wall.py ;;
     tiny)    run tiny 120 python tools/try_tiny.py ;;
     tinyvar) for so in ppls_amd/_build/${AB_GLOB_T:-libaquad_*.so}; do n=$(basename $so .so); AQ_LIB=$PWD/$so run tiny_$n 120 python tools/try_tiny.py; done ;;
     lonecoop) AQ_COOP=1 run lone_coop 120 python tools/try_single.py ;;
-    shared2) BENCH_SHARED_GPU=1 run shared2 400 python bench.py --gpus 2 --steps 4 --warmup 1 --c3-n 131072 ;;
+    shared2) BENCH_SHARED_GPU=1 run shared2 400 python bench.py --full --gpus 2 --steps 4 --warmup 1 --c3-n 131072 ;;
     diag)    run diag_1e10 120 python tools/diag_single.py --eps 1e-10 && run diag_1task 120 python tools/diag_single.py --eps 1e30 ;;
     smoke)   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     xcd)     run xcd_start 120 python tools/xcd_start.py ;;
@@ -38,8 +38,8 @@ for step in "$@"; do
     pmc)     run pmc 500 bash tools/pmc_profile.sh "pmc_$TAG" ;;
     tests_t) AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run gpu_tests_tuned 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     tests_v) AQ_LIB=$PWD/ppls_amd/_build/${TEST_LIB:?} run gpu_tests_${TEST_LIB%.so} 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
-    bench_t) AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run bench_tuned 400 python bench.py ;;
-    bench12_t) AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run bench12_tuned 400 python bench.py --eps 1e-12 --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline ;;
+    bench_t) AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run bench_tuned 400 python bench.py --full ;;
+    bench12_t) AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run bench12_tuned 400 python bench.py --full --eps 1e-12 --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline ;;
     prof_t)  AQ_LIB=$PWD/ppls_amd/_build/libaquad_t_tuned.so run prof_tuned 1000 bash tools/profile_round.sh "${TAG}t" ;;
     diagk)   run diag_k32768 300 python tools/diag_persist.py --k 32768 --reps 2 ;;
     lonevar) for so in ppls_amd/_build/${AB_GLOB_L:-libaquad_*.so}; do n=$(basename $so .so); AQ_LIB=$PWD/$so run lone_$n 120 python tools/try_single.py --reps 20; done ;;
