@@ -33,8 +33,8 @@ SOURCES = [os.path.join(CSRC, "aquad.hip")]
 # AQ_F_USER plug-in header (the reference's F(arg) macro, aquadPartA.c:46): the default Gaussian,
 # or any header named by PPLS_AMD_USER_F (see csrc/plugins/aq_user_gauss.h for the interface)
 USER_F = os.path.abspath(os.environ.get("PPLS_AMD_USER_F") or os.path.join(CSRC, "plugins", "aq_user_gauss.h"))
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("aq_libm.h", "aq_exp_table.h", "aq_sincos_table.h", "aq_device.h", "aq_stream.h",
-                                                  "aq_xsum.h", "aq_abi.inc")] + \
+# every header and include file of csrc: a new one is a dependency without being named here
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))) + \
     [os.path.join(ROOT, "include", "aquad.h"), USER_F]
 LIBS = ["-pthread", "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 

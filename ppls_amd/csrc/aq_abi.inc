@@ -5,22 +5,9 @@ using namespace aq;
 
 namespace {
 
-#ifndef AQ_LONE_NW
-#define AQ_LONE_NW 8   // waves per workgroup of unsharded lone (per-CU) launches; NW (12) for all others
-#endif
 #ifndef AQ_SYNC_SPIN
 #define AQ_SYNC_SPIN 1   // synchronous calls wait on k_fetch_sync's sequence word, not the stream
 #endif
-#ifndef AQ_TAIL_DIV
-#define AQ_TAIL_DIV 32   // r02 A/B (8192 x eps=1e-10 per launch): no tail 27.45, /64 x4 27.30, /32 x4 27.17 ms
-#endif
-#ifndef AQ_TAIL_MULT
-#define AQ_TAIL_MULT 4
-#endif
-constexpr int NSLOTS = MAXK;
-// one more, internal slot for the synchronous calls (aq_integrate / aq_integrate_shard): they never
-// touch the caller's async slots, and k_fetch_sync leaves it zeroed for the next call
-constexpr int SYNC_SLOT = NSLOTS;
 constexpr int NSLOTS_ALL = NSLOTS + 1;
 constexpr int NSTAGE = 4;          // pinned bounds staging buffers
 constexpr unsigned QCAP = 16384;
@@ -108,7 +95,7 @@ struct aq_ctx {
     int num_cus = 0;
     int grid = 0;                      // persistent workgroups per launch (one per CU, or AQ_GRID)
     std::unique_ptr<HostPool> pool;    // the batch front end's host threads (created on first use)
-    int occ[3][2][2][4] = {};          // k_stream<FID,HIST,DIAG,PCU | lone | heap>: resident workgroups per CU (0: not asked yet)
+    int occ[3][2][6] = {};             // k_stream<FID,HIST> by Variant: resident workgroups per CU (0: not asked yet)
     bool batch_heap = false;           // the batch front end's launches: the heap-seeding instance (HEAPS)
     bool coop = false;                 // AQ_COOP=1: cooperative launches
     bool histograms = true;
@@ -139,11 +126,7 @@ struct aq_ctx {
     unsigned* d_ready = nullptr;
     unsigned epoch = 0;
     LaunchHint* d_hint = nullptr;      // job-size hint carried from launch to launch
-    bool hint_valid = false;           // the workload the hint was measured on
-    bool hint_preset = false;          // the next launch takes the hint the batch pre-pass just set
-    bool hint_per_ok = false;          // the hint's per_next is current (its last writer: a HEAPS launch)
-    int hint_fid = -1, hint_nshards = 0;
-    double hint_eps = 0.0;
+    HintState hint;                    // the workload the hint was measured on (aq_launch_plan.h)
     int gsplit_env = 0;                // AQ_GSPLIT: waves per job of a multi-integral launch (0 = default)
     // level path
     DevResults* d_lres = nullptr;
@@ -230,45 +213,80 @@ int ensure_clean(aq_ctx* c, int s, int k) {
     return AQ_OK;
 }
 
+// f(std::integral_constant<int, F_...>{}) for an AQ_F_* integrand: the one place where the run-time
+// integrand becomes the kernels' FID template argument (`decltype(F)::value` in a generic lambda).
+template <typename Fn>
+auto with_fid(int integrand, Fn&& f) {
+    switch (integrand) {
+        case AQ_F_COSH4: return f(std::integral_constant<int, F_COSH4>{});
+        case AQ_F_SIN_RECIP: return f(std::integral_constant<int, F_SIN_RECIP>{});
+        default: return f(std::integral_constant<int, F_USER>{});
+    }
+}
+
+// The k_stream instance of a plan's variant. The lone instance exists only where plan_launch picks it: not
+// for the skewed integrand, and not when AQ_LONE_NW is NW (there LONE names the per-CU instance itself).
+template <int FID, bool HIST>
+const void* stream_kernel(Variant v) {
+    constexpr bool lone_ok = FID != F_SIN_RECIP && AQ_LONE_NW != NW;
+    switch (v) {
+        case Variant::DIAG_PCU: return (const void*)k_stream<FID, HIST, true, true>;
+        case Variant::DIAG: return (const void*)k_stream<FID, HIST, true, false>;
+        case Variant::PCU: return (const void*)k_stream<FID, HIST, false, true>;
+        case Variant::PLAIN: return (const void*)k_stream<FID, HIST, false, false>;
+        case Variant::LONE: return (const void*)k_stream<FID, HIST, false, true, lone_ok ? AQ_LONE_NW : NW>;
+        case Variant::HEAP: return (const void*)k_stream<FID, HIST, false, false, NW, true>;
+    }
+    return nullptr;
+}
+
+// Kernel timing (aq_kernel_timing / aq_kernel_time): a launch's event pair, reused from the free list, its
+// first event recorded ahead of the launch and its second after it; aq_kernel_time reads the pending pairs.
+using EventPair = std::pair<hipEvent_t, hipEvent_t>;
+int timing_begin(aq_ctx* ctx, EventPair& ev) {
+    if (!ctx->timing) return AQ_OK;
+    if (!ctx->ev_free.empty()) {
+        ev = ctx->ev_free.back();
+        ctx->ev_free.pop_back();
+    } else {
+        AQ_HIP(hipEventCreate(&ev.first));
+        AQ_HIP(hipEventCreate(&ev.second));
+    }
+    AQ_HIP(hipEventRecord(ev.first, ctx->stream));
+    return AQ_OK;
+}
+int timing_end(aq_ctx* ctx, const EventPair& ev) {
+    if (!ctx->timing) return AQ_OK;
+    AQ_HIP(hipEventRecord(ev.second, ctx->stream));
+    ctx->ev_pending.push_back(ev);
+    return AQ_OK;
+}
+
 // One persistent launch of k integrals (slots first_slot ..). shard_of: per-integral shard of
 // nshards (nullptr: every integral is shard `shard`). dev_bounds: the k {a, b} already on the device
 // (the batch front end copies them ahead on its own stream), else they are staged and copied here.
+// The launch's shape -- instance, waves, shares, seed depth, tail, job mode -- is plan_launch's
+// (aq_launch_plan.h); this enqueues it.
 template <int FID, bool HIST>
 int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const int32_t* shard_of, double eps,
                   int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr) {
+    static_assert(FID >= 0 && FID < 3, "aq_ctx::occ holds one row per integrand");
     const int G = ctx->grid;
-    // per-CU launches (k < PCU_MAXK) pass their bounds as kernel arguments: no staging copy
-    // (per-CU launches keep per-workgroup words: slots below NPARTS and the sync slot only)
-    const bool pcu = k < PCU_MAXK && (first_slot + k <= NPARTS || first_slot == SYNC_SLOT);
-    const bool diag = ctx->d_diag != nullptr;
-    // unsharded lone launches run AQ_LONE_NW waves per workgroup (r05, VERDICT r4 #4: the set-up and
-    // seeding of a lone integral are VALU-bound at three waves per SIMD); sharded ones keep NW, the
-    // partition the oracle restates (and every rank's shards must share)
-    // (not the skewed integrand: its lone tree sits in one small region, and 8 waves per CU measured
-    // 69.3 us against 67.3 at 12, profiles/r05k)
-    // (one integral only, k == 1: the measured case and the partition include/aquad.h documents; launches
-    // of 2-11 integrals keep NW, ADVICE r5)
-    constexpr bool lone_ok = FID != F_SIN_RECIP && AQ_LONE_NW != NW;
-    const bool lone = lone_ok && pcu && !diag && nshards == 1 && !shard_of && k == 1;
-    const int nwt = lone ? AQ_LONE_NW : NW;
-    const int W = G * nwt;
-    const void* kfn = diag ? (pcu ? (const void*)k_stream<FID, HIST, true, true> : (const void*)k_stream<FID, HIST, true, false>)
-                           : (pcu ? (const void*)k_stream<FID, HIST, false, true> : (const void*)k_stream<FID, HIST, false, false>);
-    if constexpr (lone_ok)
-        if (lone) kfn = (const void*)k_stream<FID, HIST, false, true, lone_ok ? AQ_LONE_NW : NW>;
-    // the batch front end's multi-integral launches and unsharded launches of fewer integrals than waves:
-    // the instance with heap-order seeding of whole-integral jobs and up to one job per wave (aq_stream.h
-    // HEAPS, MIN_JOB_TASKS)
-    const bool heap = !pcu && !diag && (ctx->batch_heap || (k < W && nshards == 1 && !shard_of));
-    if (heap) kfn = (const void*)k_stream<FID, HIST, false, false, NW, true>;
+    const LaunchRequest rq{FID, G, k, shard_of != nullptr, nshards, first_slot, ctx->d_diag != nullptr,
+                           ctx->batch_heap, ctx->gsplit_env, eps};
+    const LaunchPlan plan = plan_launch(rq, ctx->hint);
+    if (plan.rc) return plan.rc;   // refused before anything is enqueued
+    // per-CU launches pass their bounds as kernel arguments: no staging copy
+    const bool pcu = plan.per_cu != 0;
+    const void* kfn = stream_kernel<FID, HIST>(plan.variant);
     // Co-residency (VERDICT r3 #6): idle workgroups wait on the HBM queue for busy ones, so the whole
     // grid must be resident at once. The device's answer for this exact instance (its VGPRs, its
     // static LDS, PT threads) times the CUs must cover the grid -- checked before anything is
     // enqueued, refused with a code instead of a stall. (Other kernels sharing the device, e.g. RCCL's,
     // can still delay some workgroups' start; the no-progress stall bound then ends the launch.)
-    int& occ = ctx->occ[FID == F_SIN_RECIP ? 1 : FID == F_USER ? 2 : 0][HIST][diag][heap ? 3 : lone ? 2 : pcu];
+    int& occ = ctx->occ[FID][HIST][(int)plan.variant];
     if (occ == 0) {
-        AQ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, nwt * 64, 0));
+        AQ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, plan.nwt * 64, 0));
         if (occ < 1) occ = -1;
     }
     if (occ < 1 || (long long)occ * ctx->num_cus < (long long)G) return AQ_ERESIDENT;
@@ -301,77 +319,10 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     P.max_depth = max_depth ? max_depth : AQ_DEFAULT_MAX_DEPTH;
     P.shard = shard;
     P.nshards = nshards;
-    // jobs: one integral is split into one share per wave (the partition the oracle restates); a
-    // multi-integral launch uses gsplit-times larger shares, so one seeding pass feeds more rounds.
-    // A shard of N holds 1/N of each integral: its shares are N times fewer, so a job (and its
-    // seeding overhead) stays the same size whatever N (strong scaling).
-    // (launches of few whole integrals: LONE_GSPLIT waves per share -- with 3 only a quarter of each
-    // workgroup's waves, one per SIMD, seed, and the pool hands the others work; shards keep one share
-    // per wave, the partition oracle/aq_oracle.c restates)
-    // unsharded launches of more than a per-CU launch's integrals claim jobs (adaptive, the fill rule); the
-    // static one-share-per-wave deal stays for per-CU launches and for shards below STATIC_MAXK (r06: an
-    // unsharded 12-15-integral launch had dealt W shares of each integral statically -- every wave k jobs,
-    // k flushes onto the same k slots' lines: 392-458 us at eps=1e-10 where 11 took 152 and 16 157,
-    // profiles/r06zd)
-    const bool unsharded = nshards == 1 && !shard_of;
-    const int static_below = unsharded ? PCU_MAXK : STATIC_MAXK;
-    // (an unsharded static launch of k > 1 integrals deals ~W / k shares of each, one job per wave: with
-    // W shares each, every wave had seeded k jobs of a few hundred tasks -- cosh4 8 integrals 109 -> 75 us
-    // at eps=1e-10, 85 -> 31 us at 1e-8; the skewed sin(1/x) keeps W shares up to 4 integrals, where its
-    // heavy region wants the finer deal: 2 / 4 integrals 86 / 123 us against 94 / 132, 8 / 11 199 / 245
-    // -> 142 / 164 us; profiles/r06zf)
-    const int lone_gs = FID == F_SIN_RECIP && k <= 4 ? AQ_LONE_GSPLIT : std::max(AQ_LONE_GSPLIT, k);
-    int gs = (k >= static_below || shard_of) ? DEFAULT_GSPLIT * std::max(1, nshards) : (unsharded ? lone_gs : 1);
-    // (an unsharded launch of fewer integrals than waves, before any hint: at least one share per wave,
-    // as the hint's fill rule gives the next launches -- aq_stream.h MIN_JOB_TASKS; r06)
-    if (k >= static_below && unsharded) gs = std::min(gs, k);
-    gs = std::min(gs, W);
-    if (ctx->gsplit_env > 0) gs = ctx->gsplit_env;
-    while (gs > 1 && W % gs != 0) gs >>= 1;
-    P.shares = W / gs;
-    const bool adaptive_launch = k >= static_below && ctx->gsplit_env <= 0 && unsharded;
-    const bool same_workload = ctx->hint_valid && ctx->hint_fid == FID && ctx->hint_eps == eps &&
-                               ctx->hint_nshards == nshards;
-    // seeding keeps F and flags of every path node of a share in the wave's ring (WCAP slots)
-    const unsigned long long V = (unsigned long long)P.shares * (unsigned long long)nshards;
-    auto seed_fits = [&](int D) {
-        const unsigned long long nb = ((1ull << D) + V - 1) / V;
-        return (unsigned long long)(D + 1) * nb + 2 <= (unsigned long long)WCAP;
-    };
-    // (a lone integral seeded 1-2 levels deeper -- ~6-11 positions per share -- fell to the
-    // multi-pass seeding path: +11 us at eps=1e-10, r02; it seeds at the same depth as the rest)
-    P.D = seed_depth_job(V);
-    // the skewed integrand's unsharded lone launches seed one level deeper (the seeding's dual path,
-    // up to 128 nodes): its one heavy region then spreads over twice the positions (config-4 lone
-    // 78.8 -> 67.7 us, r04r; for cosh4 the dual path's +3 us outweighs the balance at eps=1e-10). The
-    // partition of sharded launches (the oracle's) is unchanged.
-    if (FID == F_SIN_RECIP && pcu && nshards == 1 && !shard_of) {
-        const int Dd = P.D + 1;
-        const unsigned long long nbd = ((1ull << Dd) + V - 1) / V;
-        if ((unsigned long long)(Dd + 1) * nbd + 2 <= 128ull) P.D = Dd;
-    }
-    if (!seed_fits(P.D)) return AQ_EINVAL;
-    // smaller jobs for the launch's last ~1/32 of its integrals (unsharded multi-integral launches):
-    // the end-of-launch tail (waves idle behind the longest last jobs, ~0.6 ms per launch at
-    // eps=1e-10) shrinks with the jobs drawn last. Not for shards: every shard of an integral must
-    // use the same partition, and a shard's place in its launch says nothing about where the
-    // integral's other shards sit (dist.integrate_batch_distributed packs units of different
-    // integrals and shards in any order; a sharded tail, +0.3-0.5 % per task in the bench's aligned
-    // launches, broke test_rebalanced_batch_over_rccl's counts, profiles/r04n6).
-    P.tail_from = k;
-    P.tail_mult = 1;
-    if (k >= 64 && nshards == 1 && !shard_of && ctx->gsplit_env <= 0) {
-        P.tail_from = k - std::max(1, k / AQ_TAIL_DIV);
-        P.tail_mult = AQ_TAIL_MULT;
-        // (the in-kernel hint may raise the shares; seeding then backs off to the slow path if the
-        // tail's nodes exceed one wave, never past WCAP: D grows by log2(mult) only)
-        const unsigned long long Vt = std::min<unsigned long long>(V * AQ_TAIL_MULT, (unsigned long long)W);
-        const int Dt = seed_depth_job(Vt);
-        if (!(((unsigned long long)(Dt + 1) * (((1ull << Dt) + Vt - 1) / Vt) + 2) <= (unsigned long long)WCAP)) {
-            P.tail_from = k;
-            P.tail_mult = 1;
-        }
-    }
+    P.shares = plan.shares;
+    P.D = plan.D;
+    P.tail_from = plan.tail_from;
+    P.tail_mult = plan.tail_mult;
     P.epoch = ++ctx->epoch;
     if (P.epoch == 0) P.epoch = ++ctx->epoch;
     P.qcap = QCAP;
@@ -387,48 +338,21 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     P.cellar = ctx->d_cellar;
     P.ready = ctx->d_ready;
     P.hint = ctx->d_hint;
-    P.per_cu = pcu ? 1 : 0;   // per-CU task counts for lone integrals (the reference's per-worker printout)
-    P.static_jobs = k < static_below ? 1 : 0;   // few integrals: one share per wave, static stride
-    if (P.per_cu)
+    P.per_cu = plan.per_cu;
+    P.static_jobs = plan.static_jobs;
+    if (pcu)
         for (int i = 0; i < k; ++i) P.kbounds[i] = make_double2(a[i], b[i]);
-    // multi-integral launches size their jobs from the previous launch's tasks per integral, when
-    // that launch integrated the same integrand at the same tolerance (a context that switches
-    // workload starts from the default shares and a fresh hint). Not for shards: every shard of an
-    // integral must use the same partition (shares, seed depth), and each rank's hint would come
-    // from its own, slightly different, share of the work.
-    P.adaptive = 0;
-    if (adaptive_launch) {
-        // (hint_preset: the batch front end's pre-pass set this launch's job size on the device)
-        P.adaptive = same_workload || ctx->hint_preset ? 3 : 2;
-        // per_next is written by the HEAPS instance (and the batch pre-pass's preset) only
-        if (ctx->hint_preset || (same_workload && ctx->hint_per_ok)) P.adaptive |= 4;
-        ctx->hint_per_ok = heap;
-        ctx->hint_valid = true;
-        ctx->hint_fid = FID;
-        ctx->hint_eps = eps;
-        ctx->hint_nshards = nshards;
-    }
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (ctx->timing) {
-        if (!ctx->ev_free.empty()) {
-            ev = ctx->ev_free.back();
-            ctx->ev_free.pop_back();
-        } else {
-            AQ_HIP(hipEventCreate(&ev.first));
-            AQ_HIP(hipEventCreate(&ev.second));
-        }
-        AQ_HIP(hipEventRecord(ev.first, ctx->stream));
-    }
+    P.adaptive = plan.adaptive;
+    ctx->hint = plan.hint;   // (committed before the launch: a failing launch leaves the new state)
+    EventPair ev{nullptr, nullptr};
+    if ((rc = timing_begin(ctx, ev))) return rc;
     void* args[] = {&P};
     if (ctx->coop)
-        AQ_HIP(hipLaunchCooperativeKernel(kfn, dim3(G), dim3(nwt * 64), args, 0, ctx->stream));
+        AQ_HIP(hipLaunchCooperativeKernel(kfn, dim3(G), dim3(plan.nwt * 64), args, 0, ctx->stream));
     else
-        AQ_HIP(hipLaunchKernel(kfn, dim3(G), dim3(nwt * 64), args, 0, ctx->stream));
+        AQ_HIP(hipLaunchKernel(kfn, dim3(G), dim3(plan.nwt * 64), args, 0, ctx->stream));
     ctx->qsel ^= 1;   // the launch zeroes the other block for the next one
-    if (ctx->timing) {
-        AQ_HIP(hipEventRecord(ev.second, ctx->stream));
-        ctx->ev_pending.push_back(ev);
-    }
+    if ((rc = timing_end(ctx, ev))) return rc;
     // a per-CU launch leaves its area in per-workgroup words (PCU_AREA): folded into the slots here, for
     // every reader, unless the synchronous path's own read-back folds them (k_fetch_sync, k_pack_group)
     if (pcu && !ctx->sync_fold) {
@@ -437,23 +361,19 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
         AQ_HIP(hipGetLastError());
     }
     memset(ctx->dirty + first_slot, 1, (size_t)k);
-    if (P.per_cu) memset(ctx->parts_dirty + first_slot, 1, (size_t)k);
+    if (pcu) memset(ctx->parts_dirty + first_slot, 1, (size_t)k);
     memset(ctx->slot_hist + first_slot, HIST ? 1 : 0, (size_t)k);
     return AQ_OK;
 }
 
 int launch_any(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const int32_t* shard_of,
                double eps, int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr) {
-    const bool h = ctx->histograms;
-#define AQ_LAUNCH(F)                                                                                             \
-    return h ? launch_stream<F, true>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds) \
-             : launch_stream<F, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds)
-    switch (integrand) {
-        case AQ_F_COSH4: AQ_LAUNCH(F_COSH4);
-        case AQ_F_SIN_RECIP: AQ_LAUNCH(F_SIN_RECIP);
-        default: AQ_LAUNCH(F_USER);
-    }
-#undef AQ_LAUNCH
+    return with_fid(integrand, [&](auto F) {
+        constexpr int FID = decltype(F)::value;
+        return ctx->histograms
+            ? launch_stream<FID, true>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds)
+            : launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds);
+    });
 }
 
 // Per-CU counts of one GPU in hardware-slot order (the aq_result.tasks_per_cu row).
@@ -1215,17 +1135,10 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
     DevResults* dres = ctx->d_lres;
     AQ_HIP(hipMemsetAsync(dres, 0, sizeof(DevResults), ctx->stream));
     AQ_HIP(hipMemsetAsync(ctx->d_count, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
-    switch (p->integrand) {
-        case AQ_F_COSH4:
-            hipLaunchKernelGGL((k_root<F_COSH4>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->d_front[0], ctx->d_tab);
-            break;
-        case AQ_F_SIN_RECIP:
-            hipLaunchKernelGGL((k_root<F_SIN_RECIP>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->d_front[0],
-                               ctx->d_tab);
-            break;
-        default:
-            hipLaunchKernelGGL((k_root<F_USER>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->d_front[0], ctx->d_tab);
-    }
+    with_fid(p->integrand, [&](auto F) {
+        hipLaunchKernelGGL((k_root<decltype(F)::value>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->d_front[0],
+                           ctx->d_tab);
+    });
     AQ_HIP(hipGetLastError());
     unsigned n = 1;
     int depth = 0;
@@ -1234,15 +1147,10 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
         Rec* outb = ctx->d_front[(depth + 1) & 1];
         unsigned* n_out = ctx->d_count + depth + 1;
         const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
-#define AQ_LEVEL(F)                                                                                             \
-    hipLaunchKernelGGL((k_level<F>), dim3(grid), dim3(256), 0, ctx->stream, in, n, outb, n_out,                  \
-                       (unsigned)ctx->front_cap, p->eps, depth, max_depth, dres, ctx->d_tab)
-        switch (p->integrand) {
-            case AQ_F_COSH4: AQ_LEVEL(F_COSH4); break;
-            case AQ_F_SIN_RECIP: AQ_LEVEL(F_SIN_RECIP); break;
-            default: AQ_LEVEL(F_USER);
-        }
-#undef AQ_LEVEL
+        with_fid(p->integrand, [&](auto F) {
+            hipLaunchKernelGGL((k_level<decltype(F)::value>), dim3(grid), dim3(256), 0, ctx->stream, in, n, outb, n_out,
+                               (unsigned)ctx->front_cap, p->eps, depth, max_depth, dres, ctx->d_tab);
+        });
         AQ_HIP(hipGetLastError());
         AQ_HIP(hipMemcpyAsync(ctx->h_lres, n_out, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
         AQ_HIP(hipStreamSynchronize(ctx->stream));
@@ -1296,12 +1204,11 @@ static int eval_common(aq_ctx* ctx, int integrand, bool cosh_only, size_t n, con
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
     if (cosh_only)
         hipLaunchKernelGGL((k_eval<F_COSH4, true>), dim3(grid), dim3(256), 0, ctx->stream, ctx->d_x, ctx->d_y, n, ctx->d_tab);
-    else if (integrand == AQ_F_COSH4)
-        hipLaunchKernelGGL((k_eval<F_COSH4, false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->d_x, ctx->d_y, n, ctx->d_tab);
-    else if (integrand == AQ_F_SIN_RECIP)
-        hipLaunchKernelGGL((k_eval<F_SIN_RECIP, false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->d_x, ctx->d_y, n, ctx->d_tab);
     else
-        hipLaunchKernelGGL((k_eval<F_USER, false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->d_x, ctx->d_y, n, ctx->d_tab);
+        with_fid(integrand, [&](auto F) {
+            hipLaunchKernelGGL((k_eval<decltype(F)::value, false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->d_x,
+                               ctx->d_y, n, ctx->d_tab);
+        });
     AQ_HIP(hipGetLastError());
     AQ_HIP(hipMemcpyAsync(out, ctx->d_y, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipStreamSynchronize(ctx->stream));
@@ -1503,7 +1410,7 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
     auto sorted_at = [&](size_t c) { return sort && chunks[c] >= 64; };
     auto preset_at = [&](size_t c) {
         return sorted_at(c) && ctx->gsplit_env <= 0 &&
-               !(ctx->hint_valid && ctx->hint_fid == integrand && ctx->hint_eps == eps && ctx->hint_nshards == 1);
+               !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps && ctx->hint.nshards == 1);
     };
     // the size-order pre-pass of chunk c on s_pre (after its bounds arrived; the launch waits for it)
     // (preset: a fresh workload -- no measured hint for this integrand and tolerance: the pre-pass sets
@@ -1527,13 +1434,10 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
         const unsigned blocks = (unsigned)((m + 255) / 256);
         unsigned* const cnt = ctx->d_bcnt + 2 * EST_KEYS * (c & 1u);
         unsigned* const cnt_next = ctx->d_bcnt + 2 * EST_KEYS * ((c + 1) & 1u);
-#define AQ_EST(F)                                                                                                 \
-    hipLaunchKernelGGL(k_batch_estimate<F>, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c), m, eps, \
-                       ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab)
-        if (integrand == AQ_F_COSH4) AQ_EST(F_COSH4);
-        else if (integrand == AQ_F_SIN_RECIP) AQ_EST(F_SIN_RECIP);
-        else AQ_EST(F_USER);
-#undef AQ_EST
+        with_fid(integrand, [&](auto F) {
+            hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c), m,
+                               eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
+        });
         hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c),
                            ctx->d_bkey, m, cnt, cnt + EST_KEYS, sorted_of(c),
                            perm_of(c), cnt_next, ctx->d_best + (c & 1u), ctx->d_best + ((c + 1) & 1u),
@@ -1588,12 +1492,12 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
             rc = AQ_EHIP;
             break;
         }
-        ctx->hint_preset = preset_at(c);
+        ctx->hint.preset = preset_at(c);
         ctx->batch_heap = true;
         rc = launch_any(ctx, integrand, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
                         sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c));
         ctx->batch_heap = false;
-        ctx->hint_preset = false;
+        ctx->hint.preset = false;
         mark("launched", (long)c);
         if (rc) break;
         // the rows' ring slot: chunk c - 2's copy to the host must be done before they are overwritten
@@ -1649,17 +1553,10 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
 int aq_frontier_root(aq_ctx* ctx, int integrand, double a, double b, double* d_out) {
     if (!ctx || !d_out || !integrand_ok(integrand) || !bounds_ok(integrand, a, b)) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
-    switch (integrand) {
-        case AQ_F_COSH4:
-            hipLaunchKernelGGL((k_frontier_root<F_COSH4>), dim3(1), dim3(64), 0, ctx->stream, a, b, (Rec*)d_out, ctx->d_tab);
-            break;
-        case AQ_F_SIN_RECIP:
-            hipLaunchKernelGGL((k_frontier_root<F_SIN_RECIP>), dim3(1), dim3(64), 0, ctx->stream, a, b, (Rec*)d_out,
-                               ctx->d_tab);
-            break;
-        default:
-            hipLaunchKernelGGL((k_frontier_root<F_USER>), dim3(1), dim3(64), 0, ctx->stream, a, b, (Rec*)d_out, ctx->d_tab);
-    }
+    with_fid(integrand, [&](auto F) {
+        hipLaunchKernelGGL((k_frontier_root<decltype(F)::value>), dim3(1), dim3(64), 0, ctx->stream, a, b, (Rec*)d_out,
+                           ctx->d_tab);
+    });
     AQ_HIP(hipGetLastError());
     return AQ_OK;
 }
@@ -1693,15 +1590,10 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
     if (ctx->lp_pending && (d_acc != ctx->lp_acc || ctx->lp_pending + grid > LP_CAP) && (rc = fold_pending(ctx)))
         return rc;
     LevelPart* rows = ctx->d_lparts + ctx->lp_pending;
-#define AQ_STEP(F)                                                                                           \
-    hipLaunchKernelGGL((k_level_step<F>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream, (const Rec*)d_in, n_in,  \
-                       (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows, ctx->d_tab, d_n_in)
-    switch (integrand) {
-        case AQ_F_COSH4: AQ_STEP(F_COSH4); break;
-        case AQ_F_SIN_RECIP: AQ_STEP(F_SIN_RECIP); break;
-        default: AQ_STEP(F_USER);
-    }
-#undef AQ_STEP
+    with_fid(integrand, [&](auto F) {
+        hipLaunchKernelGGL((k_level_step<decltype(F)::value>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream, (const Rec*)d_in,
+                           n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows, ctx->d_tab, d_n_in);
+    });
     AQ_HIP(hipGetLastError());
     ctx->lp_pending += grid;
     ctx->lp_acc = d_acc;
@@ -1735,15 +1627,10 @@ int aq_level_narrow(aq_ctx* ctx, int integrand, double* d_buf0, double* d_buf1, 
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
     if (levels == 0) return AQ_OK;
     AQ_HIP(hipSetDevice(ctx->device));
-#define AQ_NARROW(F)                                                                                           \
-    hipLaunchKernelGGL((k_level_narrow<F>), dim3(1), dim3(NARROW_T), 0, ctx->stream, (Rec*)d_buf0, (Rec*)d_buf1, cap, \
-                       d_counts, depth, levels, eps, max_depth, d_acc, ctx->d_tab)
-    switch (integrand) {
-        case AQ_F_COSH4: AQ_NARROW(F_COSH4); break;
-        case AQ_F_SIN_RECIP: AQ_NARROW(F_SIN_RECIP); break;
-        default: AQ_NARROW(F_USER);
-    }
-#undef AQ_NARROW
+    with_fid(integrand, [&](auto F) {
+        hipLaunchKernelGGL((k_level_narrow<decltype(F)::value>), dim3(1), dim3(NARROW_T), 0, ctx->stream, (Rec*)d_buf0,
+                           (Rec*)d_buf1, cap, d_counts, depth, levels, eps, max_depth, d_acc, ctx->d_tab);
+    });
     AQ_HIP(hipGetLastError());
     return AQ_OK;
 }

@@ -33,21 +33,13 @@
 // tasks and accepted counts -- is bit-identical whatever the schedule.
 #pragma once
 #include "aq_device.h"
+#include "aq_shape.h"
 #include "aq_xsum.h"
 
 namespace aq {
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-#ifndef AQ_PT
-#define AQ_PT 768
-#endif
-#ifndef AQ_WCAP
-#define AQ_WCAP 256
-#endif
-constexpr int PT = AQ_PT;           // threads per workgroup
-constexpr int NW = PT / 64;         // waves (workers) per workgroup: 12, three per SIMD
-constexpr int WCAP = AQ_WCAP;       // per-wave LDS ring, pairs: a round pops <= 64, pushes <= 128
 // LDS pair block, one field per array of LREC slots (SoA): a | b | fa | fm | fb | dt, the pair word
 // dt in the low half of an 8-byte field. With LREC = 50 x 64 every field of a slot lies at 0 / 50 /
 // 100 / 150 / 200 / 250 x 512 B from the slot's a -- inside the reach of ds_read2st64 /
@@ -66,10 +58,6 @@ struct DtField {
     __device__ __forceinline__ unsigned& operator[](unsigned j) const { return p[DT_STRIDE * j]; }
     __device__ __forceinline__ DtField operator+(unsigned o) const { return DtField{p + DT_STRIDE * o}; }
 };
-#ifndef AQ_S_W
-#define AQ_S_W 2
-#endif
-constexpr int S_W = AQ_S_W;              // seed depth D = floor(log2 V) + S_W: 3 or 4 positions per share
 #ifndef AQ_JOB_RUN_MAX
 #define AQ_JOB_RUN_MAX 16
 #endif
@@ -82,9 +70,6 @@ constexpr int JOB_RUN_MAX = AQ_JOB_RUN_MAX;   // most jobs one claim takes (whol
 // tiny jobs (C3 at eps=1e-3: ~1 400 tasks, ~20 us each) the last runs claimed held the launch ~0.1-0.3
 // ms past the others (DIAG: last rounds spread over ~100 us of a 512 us launch, profiles/r05a).
 constexpr unsigned GSS_DIV = AQ_GSS_DIV;
-#ifndef AQ_S_W1
-#define AQ_S_W1 2
-#endif
 #ifndef AQ_HEAP_SEED
 #define AQ_HEAP_SEED 1
 #endif
@@ -96,28 +81,6 @@ constexpr bool HEAP_SEED = AQ_HEAP_SEED != 0;
 constexpr int HEAP_D = 4;
 constexpr unsigned HEAP_NODES = (2u << HEAP_D) - 1u;   // 31 nodes + F(A), F(B): 33 lanes
 static_assert(HEAP_NODES + 2u <= 64u, "the heap seeding path is one node per lane");
-// seed depth of a job: floor(log2 V) + S_W for V = shares x shards virtual workers; a whole-integral
-// job (V = 1, tiny trees of big batches) seeds at S_W1 (its partition is the whole tree at any depth)
-__host__ __device__ constexpr int seed_depth(unsigned long long V) {
-    return V <= 1ull ? AQ_S_W1 : 63 - __builtin_clzll(V) + S_W;
-}
-// positions per share, ceil(2^D / V): with L = floor(log2 V), 2^D / V lies in (2^(D-L-1), 2^(D-L)], so a
-// count-down of at most 2^(D-L-1) steps instead of a 64-bit division (cold code at every seeding)
-__host__ __device__ constexpr unsigned seed_nb(int D, unsigned long long V) {
-    if (V <= 1ull) return 1u << D;
-    unsigned nb = 1u << (D - (63 - __builtin_clzll(V)));
-    while (nb > 1u && (unsigned long long)(nb - 1u) * V >= (1ull << D)) --nb;
-    return nb;
-}
-// a job's seed depth: seed_depth(V), one level deeper where the seeding's one-wave fast path
-// ((D + 1) levels x nb positions <= 64 nodes) still holds the deeper seeding -- the bench's adaptive
-// jobs (V ~ 24: 3 -> 6 positions per share) and whole-integral jobs (V = 1: 4 -> 8 positions); not a
-// lone launch (V = 3072: 42 -> 90 nodes). r04n A/B at 32768 integrals: -0.8 %, C3 unchanged
-// (profiles/r04n2). The oracle's shard partition restates this rule (tests' device_seed_S).
-__host__ __device__ constexpr int seed_depth_job(unsigned long long V) {
-    return (unsigned long long)(seed_depth(V) + 2) * seed_nb(seed_depth(V) + 1, V) <= 64ull
-        ? seed_depth(V) + 1 : seed_depth(V);
-}
 // q / nb for small q (seeding's lane -> node map): the float estimate q * rcp(nb), then one
 // correction each way (exact whenever the estimate is off by at most one)
 __device__ __forceinline__ unsigned div_small(unsigned q, unsigned nb, float rnb) {
@@ -204,12 +167,7 @@ enum : int { ST_ENTRY = 0, ST_INIT, ST_SEED_IN, ST_SEEDED, ST_IDLE, ST_LEAD, ST_
 constexpr int READY_STRIDE = 32;    // one ready flag per 128-B line: pollers never share a line
 constexpr int MAXG = 2048;          // max persistent workgroups per launch
 constexpr unsigned SHARE_ROT = 1021;   // static-job launches: share offset from one integral to the next
-// launches of fewer integrals keep per-workgroup (per-CU) counts and LDS exact accumulators (the LDS
-// left beside the pair block holds 12)
-constexpr int PCU_MAXK = 12;
 constexpr int PCU_ROW = PCU_MAXK - 1;   // per-CU LDS rows: tags < k < PCU_MAXK
-constexpr int STATIC_MAXK = 16;     // sharded launches of fewer integrals: one share per wave, static stride
-                                    // (unsharded: below PCU_MAXK, aq_abi.inc launch_stream)
 // The pair word dt: bits 0-7 the pair's depth (the depth of its two tasks), bits 8-30 the integral
 // (tag), bit 31 SPAN_BIT. SPAN_BIT (cosh4): the pair's interval lies where glibc's cosh takes its exp
 // path (cosh_main_span) -- set at seeding, inherited by the children (sub-intervals), so a round tests
@@ -218,31 +176,8 @@ constexpr unsigned SPAN_BIT = 1u << 31;
 constexpr int TAG_SHIFT = 8;
 constexpr unsigned TAG_MASK = (1u << 23) - 1u;
 __host__ __device__ constexpr unsigned dt_tag(unsigned dt) { return (dt >> TAG_SHIFT) & TAG_MASK; }
-// max integrals per launch: 8 x 32768, so that N = 8 ranks holding 1/8 of each integral of a batch
-// pack the same work into one launch as one GPU does with the whole batch (r04)
-constexpr int MAXK = 1 << 18;
 static_assert((unsigned)MAXK - 1u <= TAG_MASK, "the tag field must hold every integral of a launch");
-// slots whose per-CU launches keep per-workgroup words (parts), plus one row for the sync slot
-// PCU_AREA: a per-CU launch's area is kept per workgroup -- each wave adds its flushes' double-doubles
-// into its own LDS pair per integral (flush_acc), the workgroup's last wave sums its waves' into two
-// doubles beside the count words (StreamParams::parea) -- and readers add the grid's pairs into the slot's
-// exact accumulator: k_fold_parts after an asynchronous per-CU launch, k_fetch_sync / k_pack_group on the
-// synchronous and group paths. So the area of a lone integral is the correctly rounded sum of 2 x grid
-// doubles, each a double-double of its workgroup's waves' partials (no far atomic at the launch's end).
-// (r06: 16384, was 65536 -- with the per-workgroup area words beside the counts, PCU_AREA, the two blocks
-// take 134 MB where the counts alone took 268 MB)
-constexpr int NPARTS = 16384;
 __host__ __device__ __forceinline__ size_t parts_row(int slot) { return slot < NPARTS ? (size_t)slot : (size_t)NPARTS; }
-#ifndef AQ_GSPLIT_DEFAULT
-// sharded launches / first launch: 16 shares per integral over all shards (2-rank rehearsal, r03: 32 ->
-// 1.743e11, 64 -> 1.778e11, 96 -> 1.803e11; r04, per task of a launch of N x 16384 integrals sharded
-// N ways, profiles/r04n5/shard_ab.txt: 96 -> 192 = +1.3 / +0.3 / +0 % at N = 2 / 4 / 8, 384 -0.8 % at 8)
-#define AQ_GSPLIT_DEFAULT 192
-#endif
-constexpr int DEFAULT_GSPLIT = AQ_GSPLIT_DEFAULT;  // a multi-integral launch's job = the share of this many waves
-#ifndef AQ_LONE_GSPLIT
-#define AQ_LONE_GSPLIT 1   // waves per share in launches of < 16 unsharded integrals (host side, aq_abi.inc)
-#endif
 #ifndef AQ_TASKS_PER_JOB
 // A/B at 8192 integrals per launch (r01): 8k 35.4, 15k 33.7, 25k 33.6, 40k 33.1, 60k 33.3, 100k 37.0 ms;
 // r03 at the bench's 32768 per launch (profiles/r03x): 60 k -1.8 % with give / poll 64 / 128, 80 k -1.3 %;
@@ -791,7 +726,7 @@ __device__ unsigned long long g_aq_stamps[MAXG * NW * ST_STRIDE];
 #endif
 
 // NWT: waves per workgroup -- NW (12: three per SIMD) for every launch but the unsharded lone ones,
-// which run AQ_LONE_NW (aq_abi.inc launch_stream): a lone integral's set-up and seeding are VALU-bound
+// which run AQ_LONE_NW (aq_launch_plan.h plan_launch): a lone integral's set-up and seeding are VALU-bound
 // at three waves per SIMD, and its rounds are bound by one wave's heaviest share.
 template <int FID, bool HIST, bool DIAG, bool PCU, int NWT = NW, bool HEAPS = false>
 __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
@@ -1391,7 +1326,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     if (burst_cap && alive) acc.maxd = max(acc.maxd, (unsigned)D + 2u);
                     if constexpr (DIAG) cp2 = clk();
                 } else if (FID == F_SIN_RECIP && nnodes + 2u <= 128u) {
-                    // dual path (the skewed integrand's lone launches, seeded one level deeper: aq_abi.inc):
+                    // dual path (the skewed integrand's lone launches, seeded one level deeper: aq_launch_plan.h):
                     // lane q owns nodes q and q + 64 -- the fast path twice over, the two F chains
                     // interleaved, the first leaf depth from two ballots over a 128-bit column mask
                     unsigned long long c0lo = 0, c0hi = 0;   // column 0's nodes (uniform)

@@ -1,24 +1,8 @@
 // aquad.hip -- MI355X (gfx950) adaptive trapezoid quadrature: kernels + the C ABI of include/aquad.h.
 //
-// Reference: /root/reference/aquadPartA.c. Its hot path is the worker task body (:183-202) fed by
-// the farmer's LIFO bag of intervals over MPI (:125-173). Here the bag and the workers become one
-// persistent launch ("on-device farmer"):
-//   * every workgroup (one per CU) owns an LDS-resident interval stack (SoA, 33 B/record);
-//   * a round pops up to PT records, evaluates F(mid) for each in FP64 (glibc-exact cosh, aq_libm.h),
-//     applies the reference's refine test (:191), and pushes the children back with a wave
-//     ballot/mbcnt prefix scan -- no messages, no HBM traffic;
-//   * accepted areas are summed per lane in registers and reduced wave -> LDS -> one f64 atomic per
-//     workgroup at exit (the farmer's `result += buff[0]`, :149);
-//   * load balance (what the bag of tasks is for) goes through an HBM ticket queue of interval
-//     chunks: an idle workgroup takes a ticket, busy workgroups donate the bottom (shallowest,
-//     largest) part of their stack to waiting tickets, or spill when LDS is full;
-//   * termination = the token count (busy workgroups + records in published chunks) reaches zero
-//     (the farmer's `!is_empty(bag) || idle_count != workers`, :166).
-// Seeding: instead of the single root, each workgroup starts with its own cyclically dealt depth-D
-// subtrees (positions j = k*V + vwg, snake order over bands), found by a path walk whose F(mid)
-// evaluations are all independent (one parallel round); tasks above depth D are counted once, by
-// the owner of their leftmost descendant. Every decision is the reference's own arithmetic on the
-// same operands, so the interval tree -- hence tasks and accepted counts -- is bit-identical.
+// The design -- sibling pairs, one wavefront per worker with its own LDS ring, cellar / pool / HBM queue,
+// wave-local seeding, exact area accumulators -- is described at the top of aq_stream.h (k_stream). This file
+// holds the other kernels (batch size ordering, level and frontier paths, gather / reset / read-back).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (ppls_amd/build.py).
 #include <hip/hip_runtime.h>
@@ -36,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "aquad.h"
@@ -43,6 +28,7 @@
 #include "aq_libm.h"
 #include "aq_device.h"
 #include "aq_stream.h"
+#include "aq_launch_plan.h"
 #include "aq_host_pool.h"
 
 #include <rccl/rccl.h>
