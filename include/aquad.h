@@ -43,12 +43,16 @@ extern "C" {
 #define AQ_CU_SLOTS 2048      /* hardware CU slot space: xcc*256 + (se*2+sh)*16 + cu */
 #define AQ_XS_LIMBS 68        /* exact area accumulator: int64 limbs (aq_fetch_exact / aq_exact_round) */
 #define AQ_EXACT_ROW (AQ_XS_LIMBS + 4)   /* limbs, tasks, accepted, spilled, levels | error << 32 */
+#define AQ_MAX_PARAMS 4       /* most parameters per integral of the AQ_F_PARAM family (aq_param_count()) */
 
 /* Integrand = the reference's F(arg) macro (aquadPartA.c:46) as a compile-time kernel variant. */
 typedef enum {
     AQ_F_COSH4 = 0,     /* cosh(x)*cosh(x)*cosh(x)*cosh(x), glibc-2.35-exact cosh (the reference), |x| <= 170 */
     AQ_F_SIN_RECIP = 1, /* sin(1/x) (SURVEY config 4), glibc-exact for |x| > 9.5e-9 */
-    AQ_F_USER = 2       /* the plug-in compiled in from AQ_USER_F_HEADER (aq_user_integrand_name()) */
+    AQ_F_USER = 2,      /* the plug-in compiled in from AQ_USER_F_HEADER (aq_user_integrand_name()) */
+    AQ_F_PARAM = 3      /* the parametrised plug-in F(x; theta) compiled in from AQ_PARAM_F_HEADER
+                           (aq_param_integrand_name()): one parameter row per integral, through the
+                           aq_*_params entry points only -- every other entry point refuses it */
 } aq_integrand;
 
 /* Replaces the compile-time macros EPSILON / F / A / B (aquadPartA.c:45-48) and mpirun -n (:83). */
@@ -262,6 +266,28 @@ int aq_integrate_batch(aq_ctx *ctx, size_t n, const double *a, const double *b, 
 /* Device evaluation of the integrand / of cosh (libm parity checks). */
 int aq_eval_integrand(aq_ctx *ctx, int integrand, size_t n, const double *x, double *out);
 int aq_eval_cosh(aq_ctx *ctx, size_t n, const double *x, double *out);
+
+/* ---- per-integral parameters: F(x; theta_i) ----------------------------------------------------
+ * The reference's F(arg) macro is one function; AQ_F_PARAM is a FAMILY compiled in from a plug-in
+ * header (default: the Gaussian exp(-((x - mu) * s)^2), theta = {mu, s}; at {0, 1} bit for bit the
+ * AQ_F_USER Gaussian). Every integral carries its own row of aq_param_count() doubles, theta is
+ * row-major [integrals][aq_param_count()]. The calls mirror aq_eval_integrand, aq_integrate,
+ * aq_integrate_many_async and aq_integrate_batch (same slots, same readers: aq_fetch, aq_fetch_exact,
+ * aq_gather_*; same chunking, size order and AQ_BATCH_* environment) and return AQ_EINVAL for a null
+ * theta, a non-finite entry, or a row outside the family's domain. aq_integrate_params wants
+ * p->integrand == AQ_F_PARAM. The device theta buffers are allocated by the first of these calls.
+ * Not covered: aq_integrate_levels, the frontier engine (aq_level_*, aq_frontier_*) and
+ * aq_integrate_group take no theta and return AQ_EINVAL for AQ_F_PARAM. */
+int aq_param_count(void);                       /* nparams of the compiled-in family */
+const char *aq_param_integrand_name(void);
+int aq_eval_integrand_params(aq_ctx *ctx, size_t n, const double *x, const double *theta /* [n*np] */, double *out);
+int aq_integrate_params(aq_ctx *ctx, const aq_problem *p, const double *theta /* [np] */, aq_result *res);
+int aq_integrate_many_params_async(aq_ctx *ctx, int k, const double *a, const double *b,
+                                   const double *theta /* [k*np] */, double eps, int max_depth, int shard,
+                                   int nshards, int first_slot);
+int aq_integrate_batch_params(aq_ctx *ctx, size_t n, const double *a, const double *b,
+                              const double *theta /* [n*np] */, double eps, double *area, uint64_t *accepted,
+                              uint64_t *tasks);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel on the context's

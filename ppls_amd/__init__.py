@@ -7,6 +7,7 @@ hand-written HIP kernels for gfx950 behind the C ABI in include/aquad.h.
 """
 from .aquad import (  # noqa: F401
     COSH4,
+    PARAM,
     SIN_RECIP,
     USER,
     AquadError,
@@ -18,8 +19,10 @@ from .aquad import (  # noqa: F401
     farmer,
     format_reference,
     integrate,
+    param_count,
+    param_integrand_name,
     user_integrand_name,
 )
 
-__all__ = ["COSH4", "SIN_RECIP", "USER", "AquadError", "Context", "Group", "Problem", "Result", "exact_round",
-           "farmer", "format_reference", "integrate", "user_integrand_name"]
+__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "Group", "Problem", "Result", "exact_round",
+           "farmer", "format_reference", "integrate", "param_count", "param_integrand_name", "user_integrand_name"]

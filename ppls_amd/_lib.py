@@ -20,6 +20,8 @@ EXPORTS = (
     "aq_kernel_time", "aq_set_diagnostics", "aq_diagnostics", "aq_frontier_root", "aq_level_step", "aq_level_step_chained", "aq_level_narrow", "aq_level_defer_fold", "aq_frontier_integrate",
     "aq_group_create", "aq_group_unique_id", "aq_group_join", "aq_group_destroy", "aq_group_size",
     "aq_integrate_group", "aq_print_reference", "aq_print_reference_procs",
+    "aq_param_count", "aq_param_integrand_name", "aq_eval_integrand_params", "aq_integrate_params",
+    "aq_integrate_many_params_async", "aq_integrate_batch_params",
 )
 
 AQ_MAX_LEVELS = 128
@@ -27,6 +29,7 @@ AQ_CU_SLOTS = 2048
 AQ_XS_LIMBS = 68
 AQ_EXACT_ROW = AQ_XS_LIMBS + 4
 AQ_GROUP_ID_BYTES = 128
+AQ_MAX_PARAMS = 4
 
 
 class aq_problem(ctypes.Structure):
@@ -113,6 +116,12 @@ def load(build_if_missing=True):
         "aq_group_destroy": ([vp], None),
         "aq_group_size": ([vp], c_int),
         "aq_integrate_group": ([vp, P, R], c_int),
+        "aq_param_count": ([], c_int),
+        "aq_param_integrand_name": ([], ctypes.c_char_p),
+        "aq_eval_integrand_params": ([vp, ctypes.c_size_t, dp, dp, dp], c_int),
+        "aq_integrate_params": ([vp, P, dp, R], c_int),
+        "aq_integrate_many_params_async": ([vp, c_int, dp, dp, dp, c_dbl, c_int, c_int, c_int, c_int], c_int),
+        "aq_integrate_batch_params": ([vp, ctypes.c_size_t, dp, dp, dp, c_dbl, dp, up, up], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

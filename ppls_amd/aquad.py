@@ -18,7 +18,9 @@ from . import _lib
 COSH4 = 0
 SIN_RECIP = 1
 USER = 2        # the AQ_F_USER plug-in compiled into the library (default: exp(-x*x))
-INTEGRANDS = {"cosh4": COSH4, "sin_recip": SIN_RECIP, "user": USER}
+PARAM = 3       # the AQ_F_PARAM family F(x; theta) compiled into the library (default: exp(-((x - mu) * s)^2),
+                # theta = {mu, s}); one parameter row per integral, through the *_params methods only
+INTEGRANDS = {"cosh4": COSH4, "sin_recip": SIN_RECIP, "user": USER, "param": PARAM}
 
 # aquadPartA.c:45-48
 DEFAULT_EPSILON = 1e-3
@@ -85,6 +87,26 @@ def exact_round(limbs) -> float:
 
 def user_integrand_name() -> str:
     return _lib.load().aq_user_integrand_name().decode()
+
+
+def param_count() -> int:
+    """Parameters per integral of the AQ_F_PARAM family compiled into the library."""
+    return _lib.load().aq_param_count()
+
+
+def param_integrand_name() -> str:
+    return _lib.load().aq_param_integrand_name().decode()
+
+
+def _theta(theta, n):
+    """theta as a contiguous (n, param_count()) f64 array (a single row may be given flat)."""
+    t = np.ascontiguousarray(theta, np.float64)
+    npar = param_count()
+    if t.ndim == 1 and n == 1:
+        t = t.reshape(1, -1)
+    if t.ndim != 2 or t.shape != (n, npar):
+        raise ValueError(f"theta must have shape ({n}, {npar}), got {t.shape}")
+    return t
 
 
 def device_count() -> int:
@@ -306,6 +328,50 @@ class Context:
         out = np.empty_like(x)
         _check(self.L.aq_eval_integrand(self._h, integrand, x.size, _dp(x), _dp(out)), "aq_eval_integrand")
         return out
+
+    # -- per-integral parameters: F(x; theta_i) (AQ_F_PARAM) ---------------------------------
+    def eval_integrand_params(self, x, theta):
+        """F(x[i]; theta[i]) on the device: theta is (n, param_count())."""
+        x = np.ascontiguousarray(x, np.float64)
+        t = _theta(theta, x.size)
+        out = np.empty_like(x)
+        _check(self.L.aq_eval_integrand_params(self._h, x.size, _dp(x), _dp(t), _dp(out)), "aq_eval_integrand_params")
+        return out
+
+    def integrate_params(self, problem: Problem, theta) -> Result:
+        """One integral of the family, synchronously (problem.integrand must be PARAM)."""
+        t = _theta(theta, 1)
+        r = _lib.aq_result()
+        _check(self.L.aq_integrate_params(self._h, ctypes.byref(problem.c()), _dp(t), ctypes.byref(r)),
+               "aq_integrate_params")
+        return self._result(r)
+
+    def integrate_many_params_async(self, a, b, theta, eps, first_slot=0, max_depth=0, shard=0, nshards=1):
+        """integrate_many_async for the family: integral i has bounds [a[i], b[i]] and parameters theta[i]."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        t = _theta(theta, a.size)
+        _check(self.L.aq_integrate_many_params_async(self._h, a.size, _dp(a), _dp(b), _dp(t), float(eps), max_depth,
+                                                     shard, nshards, first_slot), "aq_integrate_many_params_async")
+
+    def integrate_batch_params(self, a, b, theta, eps, out=None):
+        """integrate_batch for the family: (area, tasks, accepted) per integral, in input order."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        n = a.size
+        t = _theta(theta, n)
+        if out is None:
+            area = np.empty(n, np.float64)
+            tasks = np.empty(n, np.uint64)
+            acc = np.empty(n, np.uint64)
+        else:
+            area, tasks, acc = out
+            for x, dt in ((area, np.float64), (tasks, np.uint64), (acc, np.uint64)):
+                if x.dtype != dt or x.shape != (n,) or not x.flags.c_contiguous or not x.flags.writeable:
+                    raise ValueError("out arrays must be writeable contiguous (f64, u64, u64) of the batch's size")
+        _check(self.L.aq_integrate_batch_params(self._h, n, _dp(a), _dp(b), _dp(t), float(eps), _dp(area), _up(acc),
+                                                _up(tasks)), "aq_integrate_batch_params")
+        return area, tasks, acc
 
 
 class Group:

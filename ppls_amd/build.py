@@ -34,8 +34,12 @@ SOURCES = [os.path.join(CSRC, "aquad.hip")]
 # or any header named by PPLS_AMD_USER_F (see csrc/plugins/aq_user_gauss.h for the interface)
 USER_F = os.path.abspath(os.environ.get("PPLS_AMD_USER_F") or os.path.join(CSRC, "plugins", "aq_user_gauss.h"))
 # every header and include file of csrc: a new one is a dependency without being named here
+# AQ_F_PARAM plug-in header (a family F(x; theta), one parameter row per integral): the default Gaussian
+# {mu, s}, or any header named by PPLS_AMD_PARAM_F (see csrc/plugins/aq_param_gauss.h for the interface)
+PARAM_F = os.path.abspath(os.environ.get("PPLS_AMD_PARAM_F") or os.path.join(CSRC, "plugins", "aq_param_gauss.h"))
+PLUGIN_DEFS = [f'-DAQ_USER_F_HEADER="{USER_F}"', f'-DAQ_PARAM_F_HEADER="{PARAM_F}"']
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))) + \
-    [os.path.join(ROOT, "include", "aquad.h"), USER_F]
+    [os.path.join(ROOT, "include", "aquad.h"), USER_F, PARAM_F]
 LIBS = ["-pthread", "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
 
@@ -50,7 +54,7 @@ def build_variant(name, defines, verbose=False):
     """An A/B variant of the library with extra -D flags: _build/libaquad_<name>.so (tools/ab.sh)."""
     os.makedirs(OUT, exist_ok=True)
     out = os.path.join(OUT, f"libaquad_{name}.so")
-    cmd = [HIPCC] + HIP_FLAGS + [f'-DAQ_USER_F_HEADER="{USER_F}"'] + list(defines) + ["-o", out] + SOURCES + LIBS
+    cmd = [HIPCC] + HIP_FLAGS + PLUGIN_DEFS + list(defines) + ["-o", out] + SOURCES + LIBS
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -65,7 +69,7 @@ def build(force=False, verbose=False):
     if not os.path.exists(os.path.join(CSRC, "aq_sincos_table.h")):
         subprocess.check_call([sys.executable, os.path.join(CSRC, "gen_sincos_table.py")])
     if force or _stale(LIB, DEPS):
-        cmd = [HIPCC] + HIP_FLAGS + [f'-DAQ_USER_F_HEADER="{USER_F}"', "-o", LIB] + SOURCES + LIBS
+        cmd = [HIPCC] + HIP_FLAGS + PLUGIN_DEFS + ["-o", LIB] + SOURCES + LIBS
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

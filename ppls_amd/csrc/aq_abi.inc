@@ -95,7 +95,7 @@ struct aq_ctx {
     int num_cus = 0;
     int grid = 0;                      // persistent workgroups per launch (one per CU, or AQ_GRID)
     std::unique_ptr<HostPool> pool;    // the batch front end's host threads (created on first use)
-    int occ[3][2][6] = {};             // k_stream<FID,HIST> by Variant: resident workgroups per CU (0: not asked yet)
+    int occ[4][2][6] = {};             // k_stream<FID,HIST> by Variant: resident workgroups per CU (0: not asked yet)
     bool batch_heap = false;           // the batch front end's launches: the heap-seeding instance (HEAPS)
     bool coop = false;                 // AQ_COOP=1: cooperative launches
     bool histograms = true;
@@ -157,6 +157,16 @@ struct aq_ctx {
     unsigned* d_bcnt = nullptr;        // EST_KEYS counts + EST_KEYS cursors
     double* d_best = nullptr;          // the chunk's sum of size estimates (per chunk parity)
     size_t bdev_rows = 0, bhost_cap = 0;
+    // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params; the
+    // batch rings by the first aq_integrate_batch_params): NSLOTS + 1 rows on the device beside d_bounds,
+    // their pinned staging ring, and the batch front end's rows -- two chunks' theta and two chunks' theta
+    // in size order, sized like d_bbounds / d_bsorted, and the pinned copy of the whole call
+    double* d_theta = nullptr;         // [NSLOTS_ALL][nparams]
+    double* h_theta = nullptr;         // pinned staging ring, NSTAGE x NSLOTS x nparams
+    double* d_btheta = nullptr;        // [2][btheta_rows][nparams]
+    double* d_bthsorted = nullptr;     // [2][btheta_rows][nparams] (k_batch_scatter_theta)
+    double* h_btheta = nullptr;        // [btheta_hcap][nparams]
+    size_t btheta_rows = 0, btheta_hcap = 0;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_pre = nullptr;
     // eval buffers
     double* d_x = nullptr;
@@ -269,8 +279,14 @@ int timing_end(aq_ctx* ctx, const EventPair& ev) {
 // (aq_launch_plan.h); this enqueues it.
 template <int FID, bool HIST>
 int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const int32_t* shard_of, double eps,
-                  int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr) {
-    static_assert(FID >= 0 && FID < 3, "aq_ctx::occ holds one row per integrand");
+                  int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
+                  const double* theta = nullptr, const double* dev_theta = nullptr) {
+    static_assert(FID >= 0 && FID < 4, "aq_ctx::occ holds one row per integrand");
+    // F_PARAM: the k parameter rows, on the host (staged and copied here, per-CU launches too: theta is
+    // not a kernel argument) or already on the device in the launch's order (the batch front end)
+    constexpr int NP = param::nparams;
+    const bool stage_theta = FID == F_PARAM && !dev_theta;
+    if (FID == F_PARAM && !theta && !dev_theta) return AQ_EINVAL;
     const int G = ctx->grid;
     const LaunchRequest rq{FID, G, k, shard_of != nullptr, nshards, first_slot, ctx->d_diag != nullptr,
                            ctx->batch_heap, ctx->gsplit_env, eps};
@@ -292,7 +308,7 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     if (occ < 1 || (long long)occ * ctx->num_cus < (long long)G) return AQ_ERESIDENT;
     int rc = ensure_clean(ctx, first_slot, k);
     if (rc) return rc;
-    if ((!pcu && !dev_bounds) || shard_of) {
+    if ((!pcu && !dev_bounds) || shard_of || stage_theta) {
         const int st = ctx->stage;
         ctx->stage = (st + 1) % NSTAGE;
         AQ_HIP(hipEventSynchronize(ctx->stage_ev[st]));   // the copy that last used this buffer is done
@@ -307,6 +323,12 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
             for (int i = 0; i < k; ++i) hs[i] = shard_of[i];
             AQ_HIP(hipMemcpyAsync(ctx->d_shard + first_slot, hs, sizeof(int) * (size_t)k, hipMemcpyHostToDevice,
                                   ctx->stream));
+        }
+        if (stage_theta) {
+            double* ht = ctx->h_theta + (size_t)st * NSLOTS * NP;
+            memcpy(ht, theta, sizeof(double) * (size_t)k * NP);
+            AQ_HIP(hipMemcpyAsync(ctx->d_theta + (size_t)first_slot * NP, ht, sizeof(double) * (size_t)k * NP,
+                                  hipMemcpyHostToDevice, ctx->stream));
         }
         AQ_HIP(hipEventRecord(ctx->stage_ev[st], ctx->stream));
     }
@@ -343,6 +365,7 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     if (pcu)
         for (int i = 0; i < k; ++i) P.kbounds[i] = make_double2(a[i], b[i]);
     P.adaptive = plan.adaptive;
+    if (FID == F_PARAM) P.theta = dev_theta ? dev_theta : ctx->d_theta + (size_t)first_slot * NP;
     ctx->hint = plan.hint;   // (committed before the launch: a failing launch leaves the new state)
     EventPair ev{nullptr, nullptr};
     if ((rc = timing_begin(ctx, ev))) return rc;
@@ -374,6 +397,37 @@ int launch_any(aq_ctx* ctx, int integrand, int k, const double* a, const double*
             ? launch_stream<FID, true>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds)
             : launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds);
     });
+}
+
+// The parametrised family's buffers, on the first parametrised call (a fresh context holds none of them:
+// aq_ctx_device_bytes does not move until then).
+int ensure_params(aq_ctx* ctx) {
+    if (ctx->d_theta) return AQ_OK;
+    constexpr size_t NP = (size_t)param::nparams;
+    if (!ctx->h_theta) AQ_HIP(hipHostMalloc(&ctx->h_theta, sizeof(double) * NP * NSLOTS * NSTAGE, hipHostMallocDefault));
+    return dmalloc(ctx, &ctx->d_theta, sizeof(double) * NP * NSLOTS_ALL, false);
+}
+
+// launch_any for AQ_F_PARAM (with_fid stays the three fixed integrands': no level or frontier kernel
+// is instantiated for id 3)
+int launch_params(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta, double eps, int max_depth,
+                  int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
+                  const double* dev_theta = nullptr) {
+    const int rc = ensure_params(ctx);
+    if (rc) return rc;
+    return ctx->histograms
+        ? launch_stream<F_PARAM, true>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
+                                       theta, dev_theta)
+        : launch_stream<F_PARAM, false>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
+                                        theta, dev_theta);
+}
+
+// One integral of the parametrised family: the engine's bounds rule, finite parameters, the plug-in's domain.
+bool params_ok(double a, double b, const double* th) {
+    if (!bounds_ok(AQ_F_PARAM, a, b)) return false;
+    for (int j = 0; j < param::nparams; ++j)
+        if (!std::isfinite(th[j])) return false;
+    return param::domain_ok(a, b, th);
 }
 
 // Per-CU counts of one GPU in hardware-slot order (the aq_result.tasks_per_cu row).
@@ -560,6 +614,10 @@ const char* aq_strerror(int code) {
 
 const char* aq_user_integrand_name(void) { return user::name; }
 
+int aq_param_count(void) { return param::nparams; }
+
+const char* aq_param_integrand_name(void) { return param::name; }
+
 int aq_device_count(int* count) {
     if (!count) return AQ_EINVAL;
     int n = 0;
@@ -680,6 +738,11 @@ void aq_ctx_destroy(aq_ctx* c) {
     (void)hipFree(c->d_bperm);
     (void)hipFree(c->d_bcnt);
     (void)hipFree(c->d_best);
+    (void)hipFree(c->d_theta);
+    (void)hipFree(c->d_btheta);
+    (void)hipFree(c->d_bthsorted);
+    if (c->h_theta) (void)hipHostFree(c->h_theta);
+    if (c->h_btheta) (void)hipHostFree(c->h_btheta);
     if (c->s_h2d) { (void)hipStreamSynchronize(c->s_h2d); (void)hipStreamDestroy(c->s_h2d); }
     if (c->s_pre) { (void)hipStreamSynchronize(c->s_pre); (void)hipStreamDestroy(c->s_pre); }
     if (c->s_d2h) { (void)hipStreamSynchronize(c->s_d2h); (void)hipStreamDestroy(c->s_d2h); }
@@ -880,6 +943,34 @@ int aq_integrate_shard_exact(aq_ctx* ctx, const aq_problem* p, int shard, int ns
 int aq_integrate(aq_ctx* ctx, const aq_problem* p, aq_result* res) {
     if (p && p->n_gpus > 1) return AQ_EINVAL;   // several GPUs: aq_integrate_group
     return aq_integrate_shard(ctx, p, 0, 1, res);
+}
+
+// ---- per-integral parameters (AQ_F_PARAM) -----------------------------------------------------------
+static int many_params_common(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta, double eps,
+                              int max_depth, int shard, int nshards, int first_slot, int slot_limit = NSLOTS) {
+    if (!ctx || k < 1 || k > MAXK || !a || !b || !theta) return AQ_EINVAL;
+    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
+    if (nshards < 1 || nshards > 64 || shard < 0 || shard >= nshards) return AQ_EINVAL;
+    if (first_slot < 0 || first_slot + k > slot_limit) return AQ_EINVAL;
+    for (int i = 0; i < k; ++i)
+        if (!params_ok(a[i], b[i], theta + (size_t)i * param::nparams)) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    return launch_params(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+}
+
+int aq_integrate_many_params_async(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta,
+                                   double eps, int max_depth, int shard, int nshards, int first_slot) {
+    return many_params_common(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+}
+
+int aq_integrate_params(aq_ctx* ctx, const aq_problem* p, const double* theta, aq_result* res) {
+    if (!ctx || !p || !theta) return AQ_EINVAL;
+    if (p->integrand != AQ_F_PARAM || p->n_gpus > 1 || p->n_gpus < 0) return AQ_EINVAL;
+    ctx->sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
+    const int rc = many_params_common(ctx, 1, &p->a, &p->b, theta, p->eps, p->max_depth, 0, 1, SYNC_SLOT, NSLOTS_ALL);
+    ctx->sync_fold = false;
+    if (rc) return rc;
+    return fetch_sync(ctx, res);
 }
 
 // ---- RCCL group ----------------------------------------------------------------------------------
@@ -1223,6 +1314,26 @@ int aq_eval_cosh(aq_ctx* ctx, size_t n, const double* x, double* out) {
     return eval_common(ctx, AQ_F_COSH4, true, n, x, out);
 }
 
+// (theta rides in the second half of the x buffer: n points, then n rows)
+int aq_eval_integrand_params(aq_ctx* ctx, size_t n, const double* x, const double* theta, double* out) {
+    if (!ctx || (n && (!x || !theta || !out))) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    constexpr size_t NP = (size_t)param::nparams;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const int rc = ensure_eval(ctx, n * (1 + NP));
+    if (rc) return rc;
+    double* const d_th = ctx->d_x + n;
+    AQ_HIP(hipMemcpyAsync(ctx->d_x, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(d_th, theta, n * NP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_eval_params, dim3(grid), dim3(256), 0, ctx->stream, (const double*)ctx->d_x,
+                       (const double*)d_th, ctx->d_y, n, (const ExpPair*)ctx->d_tab);
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipMemcpyAsync(out, ctx->d_y, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
 #ifndef AQ_BATCH_FIRST
 #define AQ_BATCH_FIRST 131072  // the first chunk: the host's serial work before the device starts
 #endif
@@ -1264,7 +1375,7 @@ static std::vector<int> batch_chunks(size_t n) {
 // the batch's serial host work (the first chunk's checks and staging before the device starts, the
 // last chunk's unpacking after it ends). AQ_HOST_THREADS sets the threads (default 8, the caller's
 // included; read when the pool is created).
-static_assert(AQ_F_COSH4 == F_COSH4 && AQ_F_SIN_RECIP == F_SIN_RECIP && AQ_F_USER == F_USER,
+static_assert(AQ_F_COSH4 == F_COSH4 && AQ_F_SIN_RECIP == F_SIN_RECIP && AQ_F_USER == F_USER && AQ_F_PARAM == F_PARAM,
               "the batch front end compares the C ABI's integrand ids with the kernels' FIDs");
 
 extern "C++" template <typename F>
@@ -1284,8 +1395,11 @@ static void host_parallel(aq_ctx* ctx, size_t n, size_t grain, F&& f) {
     ctx->pool->run(parts, piece);
 }
 
-int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, double eps, int integrand,
-                       double* area, uint64_t* accepted, uint64_t* tasks) {
+// theta: the parametrised family's rows [n][nparams] (integrand AQ_F_PARAM, aq_integrate_batch_params), else
+// null. The rows travel with the bounds: checked and staged with them, copied by the same stream into
+// their own device ring, carried into size order behind k_batch_scatter (k_batch_scatter_theta).
+static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
+                     int integrand, double* area, uint64_t* accepted, uint64_t* tasks) {
     // Batch front end (SURVEY config 3): up to MAXK integrals per persistent launch, every integral
     // with its own slot. Three streams (r05; profiles/r05a/c3_timeline_r04code.json had the launches
     // wait ~0.5 ms per chunk for a reset, a bounds copy, a full-width gather and a rows copy):
@@ -1302,7 +1416,9 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
     // A bad bound fails the call (AQ_EINVAL) after the chunks before it ran; the outputs are then
     // unspecified.
     if (!ctx || (n && (!a || !b))) return AQ_EINVAL;
-    if (!integrand_ok(integrand)) return AQ_EINVAL;
+    const bool par = integrand == AQ_F_PARAM;
+    constexpr size_t NP = (size_t)param::nparams;
+    if (par ? !theta : !integrand_ok(integrand)) return AQ_EINVAL;
     if (!(eps >= 0.0)) return AQ_EINVAL;
     if (n == 0) return AQ_OK;
     // AQ_BATCH_TRACE=1: the host's phase times of this call on stderr (diagnostics: tools/c3_timeline.py)
@@ -1350,6 +1466,29 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
         AQ_HIP(hipHostMalloc(&ctx->h_bbounds, sizeof(double2) * n, hipHostMallocDefault));
         ctx->bhost_cap = n;
     }
+    if (par) {
+        if ((rc = ensure_params(ctx))) return rc;
+        if (ctx->btheta_rows < rows) {
+            const size_t r0 = ctx->btheta_rows;
+            if (ctx->d_btheta) { (void)hipFree(ctx->d_btheta); ctx->dev_bytes -= sizeof(double) * NP * 2 * r0; }
+            if (ctx->d_bthsorted) { (void)hipFree(ctx->d_bthsorted); ctx->dev_bytes -= sizeof(double) * NP * 2 * r0; }
+            ctx->d_btheta = ctx->d_bthsorted = nullptr;
+            ctx->btheta_rows = 0;
+            if ((rc = dmalloc(ctx, &ctx->d_btheta, sizeof(double) * NP * 2 * rows, false))) return rc;
+            if ((rc = dmalloc(ctx, &ctx->d_bthsorted, sizeof(double) * NP * 2 * rows, false))) return rc;
+            ctx->btheta_rows = rows;
+        }
+        if (ctx->btheta_hcap < n) {
+            if (ctx->h_btheta) AQ_HIP(hipHostFree(ctx->h_btheta));
+            ctx->h_btheta = nullptr;
+            ctx->btheta_hcap = 0;
+            AQ_HIP(hipHostMalloc(&ctx->h_btheta, sizeof(double) * NP * n, hipHostMallocDefault));
+            ctx->btheta_hcap = n;
+        }
+    }
+    const size_t RT = ctx->btheta_rows;
+    auto dev_theta_of = [&](size_t c) { return ctx->d_btheta + (c & 1u) * RT * NP; };
+    auto thsorted_of = [&](size_t c) { return ctx->d_bthsorted + (c & 1u) * RT * NP; };
     // chunk c's device rings: bounds, rows and the size order at parity c & 1 (the keys live only
     // between a chunk's two pre-pass kernels, which run in order on s_pre)
     const size_t R = ctx->bdev_rows;
@@ -1434,14 +1573,21 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
         const unsigned blocks = (unsigned)((m + 255) / 256);
         unsigned* const cnt = ctx->d_bcnt + 2 * EST_KEYS * (c & 1u);
         unsigned* const cnt_next = ctx->d_bcnt + 2 * EST_KEYS * ((c + 1) & 1u);
-        with_fid(integrand, [&](auto F) {
-            hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c), m,
-                               eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
-        });
+        if (par)
+            hipLaunchKernelGGL(k_batch_estimate_params, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c),
+                               (const double*)dev_theta_of(c), m, eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
+        else
+            with_fid(integrand, [&](auto F) {
+                hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c), m,
+                                   eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
+            });
         hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c),
                            ctx->d_bkey, m, cnt, cnt + EST_KEYS, sorted_of(c),
                            perm_of(c), cnt_next, ctx->d_best + (c & 1u), ctx->d_best + ((c + 1) & 1u),
                            preset ? ctx->d_hint : nullptr, (unsigned)(ctx->grid * NW));
+        if (par)
+            hipLaunchKernelGGL(k_batch_scatter_theta, dim3((unsigned)(((size_t)m * NP + 255) / 256)), dim3(256), 0, sp,
+                               (const double*)dev_theta_of(c), (const unsigned*)perm_of(c), m, (int)NP, thsorted_of(c));
         if (hipGetLastError() != hipSuccess || hipEventRecord(ev_pre(c), sp) != hipSuccess) return AQ_EHIP;
         return AQ_OK;
     };
@@ -1449,7 +1595,12 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
     // the first chunk's is the only host work before the device starts)
     auto stage_rows = [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
-            if (!bounds_ok(integrand, a[i], b[i])) return false;
+            if (par) {
+                if (!params_ok(a[i], b[i], theta + i * NP)) return false;
+                for (size_t j = 0; j < NP; ++j) ctx->h_btheta[i * NP + j] = theta[i * NP + j];
+            } else if (!bounds_ok(integrand, a[i], b[i])) {
+                return false;
+            }
             ctx->h_bbounds[i] = make_double2(a[i], b[i]);
         }
         return true;
@@ -1462,6 +1613,9 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
             if (!o) return AQ_EINVAL;
         // the ring slot chunk c - 2 used: its readers (size pre-pass, launch) are done at its gather
         if (c >= 2 && hipStreamWaitEvent(ctx->s_h2d, ev_gath(c - 2), 0) != hipSuccess) return AQ_EHIP;
+        if (par && hipMemcpyAsync(dev_theta_of(c), ctx->h_btheta + off[c] * NP, sizeof(double) * NP * (size_t)chunks[c],
+                                  hipMemcpyHostToDevice, h2d_stream(c)) != hipSuccess)
+            return AQ_EHIP;
         if (hipMemcpyAsync(dev_bounds_of(c), ctx->h_bbounds + off[c], sizeof(double2) * (size_t)chunks[c],
                            hipMemcpyHostToDevice, h2d_stream(c)) != hipSuccess ||
             hipEventRecord(ev_h2d(c), h2d_stream(c)) != hipSuccess)
@@ -1494,8 +1648,11 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
         }
         ctx->hint.preset = preset_at(c);
         ctx->batch_heap = true;
-        rc = launch_any(ctx, integrand, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
-                        sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c));
+        rc = par ? launch_params(ctx, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
+                                 sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c),
+                                 sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c))
+                 : launch_any(ctx, integrand, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
+                              sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c));
         ctx->batch_heap = false;
         ctx->hint.preset = false;
         mark("launched", (long)c);
@@ -1548,6 +1705,18 @@ int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, 
         fprintf(stderr, "\n");
     }
     return err_from_bits(errbits);
+}
+
+int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, double eps, int integrand,
+                       double* area, uint64_t* accepted, uint64_t* tasks) {
+    if (!integrand_ok(integrand)) return AQ_EINVAL;
+    return batch_run(ctx, n, a, b, nullptr, eps, integrand, area, accepted, tasks);
+}
+
+int aq_integrate_batch_params(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
+                              double* area, uint64_t* accepted, uint64_t* tasks) {
+    if (!ctx || !theta) return AQ_EINVAL;
+    return batch_run(ctx, n, a, b, theta, eps, AQ_F_PARAM, area, accepted, tasks);
 }
 
 int aq_frontier_root(aq_ctx* ctx, int integrand, double a, double b, double* d_out) {

@@ -53,11 +53,11 @@ struct Step {
 };
 template <int FID>
 __device__ __forceinline__ Step task_step(double l, double r, double fl, double fr, double eps,
-                                          const ExpEntry* __restrict__ tab) {
+                                          const ExpEntry* __restrict__ tab, const Theta<FID>& th = Theta<FID>{}) {
     Step s;
     const double lrarea = (fl + fr) * (r - l) / 2;   // :185
     s.mid = (l + r) / 2;                             // :187
-    s.fmid = integrand<FID>(s.mid, tab);             // :188
+    s.fmid = integrand<FID>(s.mid, tab, th);         // :188
     s.larea = (fl + s.fmid) * (s.mid - l) / 2;       // :189
     s.rarea = (s.fmid + fr) * (r - s.mid) / 2;       // :190
     s.refine = fabs((s.larea + s.rarea) - lrarea) > eps;  // :191 (strict >)
@@ -81,11 +81,11 @@ struct Step2 {
 };
 //
 // Doubling needs every product to stay normal: the built-in integrands guarantee it on their
-// validated domains (aq_abi.inc bounds_ok). A plug-in F (F_USER) can be anything, so its trees use
+// validated domains (aq_abi.inc bounds_ok). A plug-in F (F_USER, F_PARAM) can be anything, so its trees use
 // the reference's expressions literally, '/2' included: area2 is then the plain larea + rarea and
 // the caller passes eps itself (area_scale<FID>() says which).
 template <int FID>
-__host__ __device__ constexpr bool doubled_areas() { return FID != F_USER; }
+__host__ __device__ constexpr bool doubled_areas() { return FID != F_USER && FID != F_PARAM; }
 // The persistent kernel's F values for cosh^4 are 16 F (integrand_k SCALED: one multiply fewer per
 // evaluation); scaling every F by the same power of two scales every product and difference of
 // :185-:191 by it exactly (nothing comes near the subnormal or overflow range on the validated
@@ -100,7 +100,7 @@ template <int FID, int K>
 __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (&r)[K], const double (&fl)[K],
                                             const double (&fr)[K], double eps2, const ExpEntry* __restrict__ tab,
                                             Step2 (&s)[K], const ExpConsts& kk = ExpConsts{}, int range_hint = -1,
-                                            unsigned long long out_mask = 0ull) {
+                                            unsigned long long out_mask = 0ull, const Theta<FID>& th = Theta<FID>{}) {
     double mid[K], fmid[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) mid[k] = (l[k] + r[k]) / 2;   // :187
@@ -115,7 +115,7 @@ __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (
         // computed HERE (volatile: not sunk below the F chains' range-check branch)
         asm volatile("" : "+v"(lr2e[k]), "+v"(wl[k]), "+v"(wr[k]));
     }
-    integrand_k<FID, K, (f_scale<FID>() != 1.0)>(mid, fmid, tab, kk, range_hint, out_mask);   // :188 (f_scale F)
+    integrand_k<FID, K, (f_scale<FID>() != 1.0)>(mid, fmid, tab, kk, range_hint, out_mask, th);   // :188 (f_scale F)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if constexpr (doubled_areas<FID>()) {
@@ -149,7 +149,7 @@ template <int FID, unsigned TABMASK = 127u>
 __device__ __forceinline__ void pair_step_halves(double ha, double hb, double fa, double fm, double fb, double eps2,
                                                  const ExpEntry* __restrict__ tab, Step2 (&s)[2], double& m,
                                                  double& hm, const ExpConsts& kk, int range_hint,
-                                                 unsigned long long out_mask) {
+                                                 unsigned long long out_mask, const Theta<FID>& th = Theta<FID>{}) {
     m = ha + hb;                                             // the parent's midpoint (:187)
     hm = 0.5 * m;
     const double mid[2] = {ha + hm, hm + hb};                // :187 for [a, m] and [m, b]
@@ -165,7 +165,7 @@ __device__ __forceinline__ void pair_step_halves(double ha, double hb, double fa
 #pragma unroll
     for (int k = 0; k < 2; ++k) asm volatile("" : "+v"(lr2e[k]), "+v"(wl[k]), "+v"(wr[k]));
     double fmid[2];
-    integrand_k<FID, 2, (f_scale<FID>() != 1.0), TABMASK>(mid, fmid, tab, kk, range_hint, out_mask);   // :188
+    integrand_k<FID, 2, (f_scale<FID>() != 1.0), TABMASK>(mid, fmid, tab, kk, range_hint, out_mask, th);   // :188
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         s[k].fmid = fmid[k];

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aquad.h"   // AQ_MAX_PARAMS
 #include "aq_exp_table.h"
 #include "aq_sincos_table.h"
 
@@ -309,7 +310,7 @@ __device__ __forceinline__ double sin_glibc(double x, const double* __restrict__
 __device__ __forceinline__ const double* sin_table(const ExpEntry* tab) { return reinterpret_cast<const double*>(tab); }
 
 // Integrand ids (include/aquad.h aq_integrand).
-enum : int { F_COSH4 = 0, F_SIN_RECIP = 1, F_USER = 2 };
+enum : int { F_COSH4 = 0, F_SIN_RECIP = 1, F_USER = 2, F_PARAM = 3 };
 
 }  // namespace aq
 
@@ -327,16 +328,48 @@ enum : int { F_COSH4 = 0, F_SIN_RECIP = 1, F_USER = 2 };
 #endif
 #include AQ_USER_F_HEADER
 
+// The AQ_F_PARAM plug-in: a FAMILY F(x; theta) with one parameter row per integral (the reference's
+// F(arg) macro with per-integral constants), chosen at build time with -DAQ_PARAM_F_HEADER=<file>
+// (ppls_amd/build.py: PPLS_AMD_PARAM_F=<file>). The header defines in namespace aq::param
+//   constexpr const char* name;                                  -- reported by aq_param_integrand_name()
+//   constexpr int nparams;                                       -- 1 .. AQ_MAX_PARAMS (aq_param_count())
+//   __device__ double F(double x, const double (&th)[nparams], const aq::ExpEntry* tab);
+//   inline bool domain_ok(double a, double b, const double* th); -- host check of one integral
+// and is compiled in as integrand id 3. It runs through the persistent kernel and the batch front end
+// only (aq_integrate_params, aq_integrate_many_params_async, aq_integrate_batch_params,
+// aq_eval_integrand_params): the level-synchronous path, the frontier engine and aq_integrate_group
+// take no theta and refuse id 3. Like AQ_F_USER its trees use the reference's area expressions
+// literally. In k_stream theta is wave-uniform and reloaded with a scalar load wherever the wave's
+// integral changes (aq_stream.h sload_theta); the rounds carry no per-lane parameter traffic.
+#ifndef AQ_PARAM_F_HEADER
+#define AQ_PARAM_F_HEADER "plugins/aq_param_gauss.h"
+#endif
+#include AQ_PARAM_F_HEADER
+
 namespace aq {
+
+static_assert(param::nparams >= 1 && param::nparams <= AQ_MAX_PARAMS, "AQ_F_PARAM: 1 .. AQ_MAX_PARAMS parameters");
+
+// An integral's parameters as the device code passes them: nothing for the fixed integrands (an empty
+// argument that vanishes), the row theta[nparams] for F_PARAM.
+template <int FID>
+struct Theta {};
+template <>
+struct Theta<F_PARAM> {
+    double v[param::nparams];
+};
 
 // F(arg) exactly as the reference macro expands (aquadPartA.c:46): ((c*c)*c)*c.
 template <int FID>
-__device__ __forceinline__ double integrand(double x, const ExpEntry* __restrict__ tab) {
+__device__ __forceinline__ double integrand(double x, const ExpEntry* __restrict__ tab,
+                                            const Theta<FID>& th = Theta<FID>{}) {
     if constexpr (FID == F_COSH4) {
         const double c = cosh_glibc(x, tab);
         return c * c * c * c;
     } else if constexpr (FID == F_USER) {
         return user::F(x, tab);
+    } else if constexpr (FID == F_PARAM) {
+        return param::F(x, th.v, tab);
     } else {
         return sin_glibc(AQ_SIN_RECIP_RN ? recip_rn(x) : 1.0 / x, sin_table(tab));   // config 4: sin(1.0/(arg))
     }
@@ -452,7 +485,7 @@ __device__ __forceinline__ bool cosh_main_span(double lo, double hi) {
 template <int FID, int K, bool SCALED = false, unsigned TABMASK = 127u>
 __device__ __forceinline__ void integrand_k(const double (&x)[K], double (&f)[K], const ExpEntry* __restrict__ tab,
                                             const ExpConsts& kk = ExpConsts{}, int range_hint = -1,
-                                            unsigned long long out_mask = 0ull) {
+                                            unsigned long long out_mask = 0ull, const Theta<FID>& th = Theta<FID>{}) {
     if constexpr (FID == F_COSH4) {
         constexpr double cs = SCALED ? 2.0 : 1.0;   // c[k] holds cs * cosh
         double c[K];
@@ -485,13 +518,16 @@ __device__ __forceinline__ void integrand_k(const double (&x)[K], double (&f)[K]
     } else if constexpr (FID == F_USER) {
 #pragma unroll
         for (int k = 0; k < K; ++k) f[k] = user::F(x[k], tab);
+    } else if constexpr (FID == F_PARAM) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) f[k] = param::F(x[k], th.v, tab);
     } else {
 #pragma unroll
         for (int k = 0; k < K; ++k) f[k] = sin_glibc(AQ_SIN_RECIP_RN ? recip_rn(x[k]) : 1.0 / x[k], sin_table(tab));
     }
 }
 
-// A kernel's LDS integrand table: glibc exp's 128 entries (cosh^4 and the plug-ins), or for sin(1/x)
+// A kernel's LDS integrand table: glibc exp's 128 entries (cosh^4 and the plug-ins, ids 2 and 3), or for sin(1/x)
 // glibc's __sincostab (444 doubles in 222 16-B entries) -- integrand<F_SIN_RECIP> reads `tab` as that.
 template <int FID>
 constexpr int ftab_entries() { return FID == F_SIN_RECIP ? (AQ_SINCOS_TAB_N + 1) / 2 : 128; }

@@ -417,6 +417,8 @@ struct StreamParams {
                                     // with the launch's other arguments, not a cold HBM line at seeding)
     int adaptive;                   // bit 0: take shares per integral from hint->shares_next; bit 1: update it;
                                     // bit 2: hint->per_next belongs to it (the HEAPS instance's fill rule)
+    const double* theta;            // F_PARAM: [nprob][param::nparams] row-major, integral p's row at p * nparams
+                                    // (device memory, written before the launch; else null)
 };
 
 // Diagnostics record per workgroup (aq_set_diagnostics), accumulated in LDS by every wave:
@@ -619,6 +621,37 @@ __device__ __forceinline__ double2 sload_bounds(const double2* base, int p) {
     u32x4 r;
     asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(addr) : "memory");
     return make_double2(__hiloint2double((int)r.y, (int)r.x), __hiloint2double((int)r.w, (int)r.z));
+}
+
+// Integral p's parameter row (F_PARAM) through the scalar data cache, as sload_bounds fetches {a, b}: the
+// same readfirstlane address, the same wait. The host's copy (or the batch pre-pass's scatter kernel)
+// wrote the row before the launch, so the scalar cache holds nothing stale. The wave calls it wherever
+// its integral (`tag`) is assigned -- th stays wave-uniform, in SGPRs, and the rounds load nothing.
+// The other integrands' Theta is empty: nothing is loaded.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+template <int FID>
+__device__ __forceinline__ void sload_theta(Theta<FID>& th, const double* base, int p) {
+    if constexpr (FID == F_PARAM) {
+        constexpr int NP = param::nparams;
+        const unsigned long long a64 = (unsigned long long)(base + (size_t)p * NP);
+        const unsigned long long addr = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a64 >> 32)) << 32) |
+                                        (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a64);
+#pragma unroll
+        for (int i = 0; i < NP; i += 2) {
+            const unsigned long long ai = addr + 8ull * (unsigned)i;
+            if (i + 1 < NP) {
+                u32x4 r;
+                asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(ai) : "memory");
+                th.v[i] = __hiloint2double((int)r.y, (int)r.x);
+                th.v[i + 1 < NP ? i + 1 : i] = __hiloint2double((int)r.w, (int)r.z);   // (i + 1 < NP here: the index
+                                                                                        // is clamped for the dead instance only)
+            } else {
+                u32x2 r;
+                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(ai) : "memory");
+                th.v[i] = __hiloint2double((int)r.y, (int)r.x);
+            }
+        }
+    }
 }
 
 // One slot's six fields from / to ONE LDS address (the slot's a, in bytes): the fields lie at 0 / 50 /
@@ -869,6 +902,8 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
 
     Acc acc{0.0, 0.0, 0u, 0u, 0u, 0u, 0u, 0u};
     int tag = 0;                  // integral the accumulators belong to (wave-uniform)
+    Theta<FID> th{};              // its parameter row (F_PARAM; wave-uniform), reloaded wherever tag is assigned
+    sload_theta<FID>(th, P.theta, tag);
     unsigned ctop = 0;            // pairs in this wave's cellar (wave-uniform)
     Cellar* __restrict__ cel = P.cellar + w_all;
     // the job this wave seeds next (wave-uniform). Launches of few integrals (static jobs) number the
@@ -1093,6 +1128,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                 if (ptag != tag) {     // the ring's new integral
                     flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
                     tag = ptag;
+                    sload_theta<FID>(th, P.theta, tag);
                 }
                 bot = 0;
                 top = k;
@@ -1149,6 +1185,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                 if (p != tag) {
                     flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
                     tag = p;
+                    sload_theta<FID>(th, P.theta, tag);
                 }
                 if constexpr (AQ_STAMPS && !DIAG) {
                     const unsigned long long cf1 = clk();
@@ -1223,7 +1260,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     }
                     mid = (l + r) / 2;                                            // :187
                     if (q < HEAP_NODES + 2u) {
-                        fmid = integrand<FID>(isnode ? mid : (q == HEAP_NODES ? A : B), tab);   // :188
+                        fmid = integrand<FID>(isnode ? mid : (q == HEAP_NODES ? A : B), tab, th);   // :188
                         fm[q] = fmid;
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -1283,10 +1320,10 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     if constexpr (DIAG) { asm volatile("" :: "v"(mid)); cb = clk(); }
                     const unsigned fq = nnodes + 2 <= 64 ? q : (q < nnodes ? q : 64u);
                     if (fq < nnodes + 2)
-                        fmid = integrand<FID>(isnode ? mid : (q == nnodes ? A : B), tab);   // :188
+                        fmid = integrand<FID>(isnode ? mid : (q == nnodes ? A : B), tab, th);   // :188
                     if (fq < nnodes + 2) fm[q] = fmid;
                     if constexpr (AQ_STAMPS && !DIAG) { asm volatile("" :: "v"(fmid)); stamp(ST_FEVAL); }
-                    if (nnodes + 2 > 64 && lane < 2) fm[nnodes + lane] = integrand<FID>(lane == 0 ? A : B, tab);
+                    if (nnodes + 2 > 64 && lane < 2) fm[nnodes + lane] = integrand<FID>(lane == 0 ? A : B, tab, th);
                     if constexpr (DIAG) {
                         cp1 = clk();
                         if (lane == 0) {
@@ -1362,7 +1399,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     for (int h = 0; h < 2; ++h) {
                         const unsigned q = lane + 64u * (unsigned)h;
                         fx[h] = 0.0;
-                        if (q < nnodes + 2u) fx[h] = integrand<FID>(isn[h] ? mx[h] : (q == nnodes ? A : B), tab);   // :188
+                        if (q < nnodes + 2u) fx[h] = integrand<FID>(isn[h] ? mx[h] : (q == nnodes ? A : B), tab, th);   // :188
                     }
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -1434,7 +1471,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                             } else {
                                 x = (q == nnodes) ? A : B;
                             }
-                            fm[q] = integrand<FID>(x, tab);
+                            fm[q] = integrand<FID>(x, tab, th);
                         }
                     }
                     if constexpr (DIAG) cp1 = clk();
@@ -1875,7 +1912,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             if constexpr (FID == F_COSH4) nospan = __ballot((int)dt >= 0);
             double pm, hm;
             pair_step_halves<FID, WIDE ? 255u : 127u>(pa, pb, pfa, pfm, pfb, eps2, tab, st, pm, hm, kk,
-                                                       FID == F_COSH4 ? 2 : -1, nospan & am);
+                                                       FID == F_COSH4 ? 2 : -1, nospan & am, th);
             if constexpr (prio_by_load) { if (!b_heavy) asm volatile("s_setprio 0"); }
             const unsigned long long r0m = __ballot(st[0].refine), r1m = __ballot(st[1].refine);
             unsigned long long okm = am;

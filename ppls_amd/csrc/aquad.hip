@@ -80,6 +80,22 @@ __global__ __launch_bounds__(256) void k_eval(const double* __restrict__ x, doub
     }
 }
 
+// F_PARAM at n points, each with its own parameter row theta[i * nparams ..] (aq_eval_integrand_params).
+__global__ __launch_bounds__(256) void k_eval_params(const double* __restrict__ x, const double* __restrict__ theta,
+                                                     double* __restrict__ out, size_t n,
+                                                     const ExpPair* __restrict__ gtab) {
+    __shared__ ExpEntry tab[ftab_entries<F_PARAM>()];
+    stage_f_table<F_PARAM>(tab, gtab);
+    __syncthreads();
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = gid; i < n; i += stride) {
+        Theta<F_PARAM> th;
+#pragma unroll
+        for (int j = 0; j < param::nparams; ++j) th.v[j] = theta[i * param::nparams + j];
+        out[i] = integrand<F_PARAM>(x[i], tab, th);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Batch ordering (aq_integrate_batch, r05): a launch of whole tiny trees ends when its last-claimed jobs
 // do, so the batch front end hands its launches their integrals largest first. The size of a tree is
@@ -100,10 +116,12 @@ constexpr double EST_PER_OCTAVE = 8.0;
 // mean at 1e-3 and 1e-10 (an offline check with the host integrand), so a fresh workload's first launch
 // can size its jobs from it (k_batch_scatter)
 constexpr double EST_TASKS = 2.84;
+// (theta: F_PARAM's parameter rows, integral i's at theta[i * nparams ..]; the other integrands pass null)
 template <int FID>
-__global__ __launch_bounds__(256) void k_batch_estimate(const double2* __restrict__ bounds, int n, double eps,
-                                                        unsigned* __restrict__ key_of, unsigned* __restrict__ counts,
-                                                        double* __restrict__ est_sum, const ExpPair* __restrict__ gtab) {
+__device__ __forceinline__ void batch_estimate(const double2* __restrict__ bounds, int n, double eps,
+                                               unsigned* __restrict__ key_of, unsigned* __restrict__ counts,
+                                               double* __restrict__ est_sum, const ExpPair* __restrict__ gtab,
+                                               const double* __restrict__ theta) {
     __shared__ ExpEntry tab[ftab_entries<FID>()];
     __shared__ unsigned s_cnt[EST_KEYS];
     __shared__ double s_est[4];
@@ -114,6 +132,11 @@ __global__ __launch_bounds__(256) void k_batch_estimate(const double2* __restric
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i < n) {
         const double2 ab = bounds[i];
+        Theta<FID> th{};
+        if constexpr (FID == F_PARAM) {
+#pragma unroll
+            for (int j = 0; j < param::nparams; ++j) th.v[j] = theta[(size_t)i * param::nparams + j];
+        }
         double x[17], f[17];
         x[0] = ab.x;
         x[16] = ab.y;
@@ -122,7 +145,7 @@ __global__ __launch_bounds__(256) void k_batch_estimate(const double2* __restric
 #pragma unroll
             for (int k = s; k < 16; k += 2 * s) x[k] = (x[k - s] + x[k + s]) / 2;
 #pragma unroll
-        for (int k = 0; k < 17; ++k) f[k] = integrand<FID>(x[k], tab);   // :188
+        for (int k = 0; k < 17; ++k) f[k] = integrand<FID>(x[k], tab, th);   // :188
         bool alive[16] = {true};
 #pragma unroll
         for (int d = 0, s = 16; d < 4; ++d, s >>= 1) {
@@ -153,6 +176,20 @@ __global__ __launch_bounds__(256) void k_batch_estimate(const double2* __restric
     __syncthreads();
     if (threadIdx.x < EST_KEYS && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
     if (threadIdx.x == 0) atomicAdd(est_sum, (s_est[0] + s_est[1]) + (s_est[2] + s_est[3]));
+}
+template <int FID>
+__global__ __launch_bounds__(256) void k_batch_estimate(const double2* __restrict__ bounds, int n, double eps,
+                                                        unsigned* __restrict__ key_of, unsigned* __restrict__ counts,
+                                                        double* __restrict__ est_sum, const ExpPair* __restrict__ gtab) {
+    static_assert(FID != F_PARAM, "the parametrised family's estimate takes theta (k_batch_estimate_params)");
+    batch_estimate<FID>(bounds, n, eps, key_of, counts, est_sum, gtab, nullptr);
+}
+__global__ __launch_bounds__(256) void k_batch_estimate_params(const double2* __restrict__ bounds,
+                                                               const double* __restrict__ theta, int n, double eps,
+                                                               unsigned* __restrict__ key_of,
+                                                               unsigned* __restrict__ counts, double* __restrict__ est_sum,
+                                                               const ExpPair* __restrict__ gtab) {
+    batch_estimate<F_PARAM>(bounds, n, eps, key_of, counts, est_sum, gtab, theta);
 }
 
 // Scatter the chunk into size order: sorted[pos] = bounds[i], perm[pos] = i, pos = the key's offset (an
@@ -211,6 +248,18 @@ __global__ __launch_bounds__(256) void k_batch_scatter(const double2* __restrict
         sorted[pos] = bounds[i];
         perm[pos] = (unsigned)i;
     }
+}
+
+// The parameter rows of a size-ordered chunk (aq_integrate_batch_params), after k_batch_scatter on the same
+// stream: sorted position pos holds integral perm[pos], so its row follows its bounds into the launch's order
+// (a sorted theta buffer per chunk parity; the launch then reads theta by tag, like the bounds).
+__global__ __launch_bounds__(256) void k_batch_scatter_theta(const double* __restrict__ theta,
+                                                             const unsigned* __restrict__ perm, int n, int np,
+                                                             double* __restrict__ sorted) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * (size_t)np) return;
+    const size_t pos = i / (size_t)np, j = i - pos * (size_t)np;
+    sorted[i] = theta[(size_t)perm[pos] * (size_t)np + j];
 }
 
 // ------------------------------------------------------------------------------------------------

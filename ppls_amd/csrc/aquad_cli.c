@@ -1,7 +1,8 @@
 /*
  * aquad_cli.c -- drop-in for `mpirun -n P ./aquadPartA` (/root/reference/aquadPartA.c main(), :78-123).
  *
- *   aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user] [--per-cu] [--levels]
+ *   aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] [--theta v0,v1,...]
+ *         [--per-cu] [--levels]
  *
  * Same observable surface as the reference: `Area=%lf`, a blank line, `Tasks Per Process`, the index
  * row and the count row (tab-terminated entries). Process 0 is the farmer and always reports 0 tasks
@@ -11,6 +12,8 @@
  * reference's error exactly (:86-90). Defaults are the reference's macros (:45-48).
  * With G > 1 the run is sharded over an RCCL group (aq_group_create: one host thread drives every
  * GPU; aq_integrate_group combines the shards with one grouped all-reduce / all-gather).
+ * `--f param --theta v0,v1,...` integrates the parametrised family F(x; theta) (aq_integrate_params; as many
+ * values as aq_param_count(); one GPU). The printout is the same.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -21,13 +24,15 @@
 
 static void usage(void) {
     fprintf(stderr,
-            "usage: aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user] [--per-cu] "
-            "[--levels]\n");
+            "usage: aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] "
+            "[--theta v0,v1,...] [--per-cu] [--levels]\n");
 }
 
 int main(int argc, char **argv) {
     aq_problem p = {AQ_F_COSH4, 0, 0.0, 5.0, 1e-3, 0, 0}; /* aquadPartA.c:45-48 */
     int nprocs = -1, gpus = 1, per_cu = 0, levels = 0;
+    double theta[AQ_MAX_PARAMS] = {0};
+    int ntheta = 0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -40,11 +45,28 @@ int main(int argc, char **argv) {
             if (!strcmp(v, "cosh4")) p.integrand = AQ_F_COSH4;
             else if (!strcmp(v, "sin_recip")) p.integrand = AQ_F_SIN_RECIP;
             else if (!strcmp(v, "user")) p.integrand = AQ_F_USER;
+            else if (!strcmp(v, "param")) p.integrand = AQ_F_PARAM;
             else { usage(); return 2; }
+            ++i;
+        } else if (!strcmp(a, "--theta") && v) {
+            const char *s = v;
+            for (ntheta = 0; *s;) {
+                char *end;
+                const double x = strtod(s, &end);
+                if (end == s || ntheta == AQ_MAX_PARAMS) { usage(); return 2; }
+                theta[ntheta++] = x;
+                s = *end == ',' ? end + 1 : end;
+                if (*end && *end != ',') { usage(); return 2; }
+            }
             ++i;
         } else if (!strcmp(a, "--per-cu")) per_cu = 1;
         else if (!strcmp(a, "--levels")) levels = 1;
         else { usage(); return 2; }
+    }
+    if (p.integrand == AQ_F_PARAM ? (ntheta != aq_param_count() || gpus != 1) : ntheta != 0) {
+        fprintf(stderr, "aquad: --f param takes --theta with %d value(s) (%s) on one GPU; no other integrand takes it\n",
+                aq_param_count(), aq_param_integrand_name());
+        return 2;
     }
     if (nprocs == -1) nprocs = 1 + gpus;
     if (nprocs < 2) { /* aquadPartA.c:86-90 */
@@ -69,7 +91,7 @@ int main(int argc, char **argv) {
     res.tasks_per_cu = cu;
     if (rc == AQ_OK) {
         if (gpus == 1) {
-            rc = aq_integrate(ctx[0], &p, &res);
+            rc = p.integrand == AQ_F_PARAM ? aq_integrate_params(ctx[0], &p, theta, &res) : aq_integrate(ctx[0], &p, &res);
         } else {
             p.n_gpus = gpus;
             rc = aq_group_create(ctx, gpus, &grp);
