@@ -289,6 +289,38 @@ int aq_integrate_batch_params(aq_ctx *ctx, size_t n, const double *a, const doub
                               const double *theta /* [n*np] */, double eps, double *area, uint64_t *accepted,
                               uint64_t *tasks);
 
+/* ---- error estimate and extrapolated area ------------------------------------------------------
+ * EPSILON bounds each accepted interval's difference d = (larea + rarea) - lrarea (:191), not the
+ * result. The _err calls run the same interval tree (area, tasks, accepted and levels as the plain
+ * calls give them) and also sum d over the accepted tasks, at no extra F evaluation:
+ *   err_abs    = Σ|d|  an estimate of the area's error (what QUADPACK calls abserr);
+ *   err_signed = Σd    one Richardson (Simpson) step: area + err_signed / 3 (aq_err_extrapolate).
+ * Each term is the reference's own value; the sums are plain double sums in a schedule-dependent order
+ * (within accepted * 2^-52 * err_abs of the exact sums). They have no exact-row form; an integral's
+ * shards' sums add up to the whole integral's.
+ * theta is the AQ_F_PARAM row(s) ([np] / [k*np] / [n*np]) and must be non-NULL exactly when the
+ * integrand is AQ_F_PARAM (validated as the _params calls do), else AQ_EINVAL. The calls mirror
+ * aq_integrate, aq_integrate_many_async and aq_integrate_batch (same slots; aq_fetch, aq_fetch_exact and
+ * aq_gather_* read an ERR slot as any other; same chunking, size order and AQ_BATCH_* environment; either
+ * of the batch's two error outputs may be NULL as its other outputs may). aq_fetch_err waits for the
+ * slot like aq_fetch and returns AQ_EINVAL unless the slot's last launch was an _err launch; any launch
+ * into a slot zeroes its sums first. An _err launch runs 8 waves per workgroup whatever its shape (every
+ * _err launch of one nshards deals one partition), keeps no level histograms or diagnostics (levels is
+ * reported) and leaves per-CU counts as the plain calls do. The device buffers are allocated by the
+ * first of these calls.
+ * Not covered: aq_integrate_mixed_async, aq_integrate_group, aq_integrate_levels and the frontier
+ * engine (aq_level_*, aq_frontier_*) have no _err form. */
+typedef struct { double err_abs, err_signed; } aq_err;   /* Σ|d|, Σd over accepted tasks, d = (larea+rarea)-lrarea (:191) */
+double aq_err_extrapolate(double area, const aq_err *e);  /* host: area + err_signed / 3 (one Richardson step) */
+int aq_integrate_err(aq_ctx *ctx, const aq_problem *p, const double *theta, aq_result *res, aq_err *err);
+int aq_integrate_many_err_async(aq_ctx *ctx, int integrand, int k, const double *a, const double *b,
+                                const double *theta, double eps, int max_depth, int shard, int nshards,
+                                int first_slot);
+int aq_fetch_err(aq_ctx *ctx, int slot, aq_err *err);
+int aq_integrate_batch_err(aq_ctx *ctx, size_t n, const double *a, const double *b, const double *theta, double eps,
+                           int integrand, double *area, uint64_t *accepted, uint64_t *tasks, double *err_abs,
+                           double *err_signed);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel on the context's
  * stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */

@@ -22,6 +22,7 @@ EXPORTS = (
     "aq_integrate_group", "aq_print_reference", "aq_print_reference_procs",
     "aq_param_count", "aq_param_integrand_name", "aq_eval_integrand_params", "aq_integrate_params",
     "aq_integrate_many_params_async", "aq_integrate_batch_params",
+    "aq_err_extrapolate", "aq_integrate_err", "aq_integrate_many_err_async", "aq_fetch_err", "aq_integrate_batch_err",
 )
 
 AQ_MAX_LEVELS = 128
@@ -45,6 +46,10 @@ class aq_result(ctypes.Structure):
                 ("tasks_per_gpu", ctypes.POINTER(ctypes.c_uint64)), ("tasks_per_cu", ctypes.POINTER(ctypes.c_uint64))]
 
 
+class aq_err(ctypes.Structure):
+    _fields_ = [("err_abs", ctypes.c_double), ("err_signed", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -62,6 +67,7 @@ def load(build_if_missing=True):
     up = ctypes.POINTER(ctypes.c_uint64)
     P = ctypes.POINTER(aq_problem)
     R = ctypes.POINTER(aq_result)
+    E = ctypes.POINTER(aq_err)
     ip = ctypes.POINTER(ctypes.c_int32)
     lp = ctypes.POINTER(ctypes.c_int64)
     c_int, c_dbl = ctypes.c_int, ctypes.c_double
@@ -122,6 +128,11 @@ def load(build_if_missing=True):
         "aq_integrate_params": ([vp, P, dp, R], c_int),
         "aq_integrate_many_params_async": ([vp, c_int, dp, dp, dp, c_dbl, c_int, c_int, c_int, c_int], c_int),
         "aq_integrate_batch_params": ([vp, ctypes.c_size_t, dp, dp, dp, c_dbl, dp, up, up], c_int),
+        "aq_err_extrapolate": ([c_dbl, E], c_dbl),
+        "aq_integrate_err": ([vp, P, dp, R, E], c_int),
+        "aq_integrate_many_err_async": ([vp, c_int, c_int, dp, dp, dp, c_dbl, c_int, c_int, c_int, c_int], c_int),
+        "aq_fetch_err": ([vp, c_int, E], c_int),
+        "aq_integrate_batch_err": ([vp, ctypes.c_size_t, dp, dp, dp, c_dbl, c_int, dp, up, up, dp, dp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

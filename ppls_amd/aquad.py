@@ -63,6 +63,11 @@ class Result:
     tasks_per_level: List[int] = field(default_factory=list)
     leaves_per_level: List[int] = field(default_factory=list)
     tasks_per_gpu: List[int] = field(default_factory=list)
+    # the error estimate (Context.integrate_err): Σ|d| and Σd over the accepted tasks, d = (larea + rarea) -
+    # lrarea (aquadPartA.c:191), and the one-step Richardson value area + err_signed / 3; None from every other call
+    err_abs: Optional[float] = None
+    err_signed: Optional[float] = None
+    area_extrapolated: Optional[float] = None
 
 
 def _check(rc, what):
@@ -372,6 +377,67 @@ class Context:
         _check(self.L.aq_integrate_batch_params(self._h, n, _dp(a), _dp(b), _dp(t), float(eps), _dp(area), _up(acc),
                                                 _up(tasks)), "aq_integrate_batch_params")
         return area, tasks, acc
+
+
+    # -- error estimate and extrapolated area (the _err calls) --------------------------------
+    def _err_theta(self, integrand, theta, n):
+        """The theta argument of an _err call: the rows' pointer for PARAM (shape checked), else None."""
+        if integrand == PARAM:
+            if theta is None:
+                raise ValueError("the PARAM integrand needs theta")
+            return _theta(theta, n)
+        if theta is not None:
+            raise ValueError("theta goes with the PARAM integrand only")
+        return None
+
+    def integrate_err(self, problem: Problem, theta=None) -> Result:
+        """integrate (or, with theta, integrate_params) with the error estimate: the same tree, and the result's
+        err_abs, err_signed and area_extrapolated filled. No level histograms (levels is reported)."""
+        pc = problem.c()
+        t = self._err_theta(pc.integrand, theta, 1)
+        r = _lib.aq_result()
+        e = _lib.aq_err()
+        _check(self.L.aq_integrate_err(self._h, ctypes.byref(pc), None if t is None else _dp(t), ctypes.byref(r),
+                                       ctypes.byref(e)), "aq_integrate_err")
+        out = self._result(r)
+        out.tasks_per_level, out.leaves_per_level = [], []
+        out.err_abs, out.err_signed = e.err_abs, e.err_signed
+        out.area_extrapolated = self.L.aq_err_extrapolate(r.area, ctypes.byref(e))
+        return out
+
+    def integrate_many_err_async(self, a, b, eps, first_slot=0, integrand=COSH4, theta=None, max_depth=0, shard=0,
+                                 nshards=1):
+        """integrate_many_async (or, with theta, integrate_many_params_async) as an error-estimate launch:
+        fetch / fetch_exact / gather_* read the slots as ever, fetch_err their two sums."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        t = self._err_theta(integrand, theta, a.size)
+        _check(self.L.aq_integrate_many_err_async(self._h, integrand, a.size, _dp(a), _dp(b),
+                                                  None if t is None else _dp(t), float(eps), max_depth, shard, nshards,
+                                                  first_slot), "aq_integrate_many_err_async")
+
+    def fetch_err(self, slot: int):
+        """(err_abs, err_signed) of a slot whose last launch was an error-estimate launch; waits for it."""
+        e = _lib.aq_err()
+        _check(self.L.aq_fetch_err(self._h, slot, ctypes.byref(e)), "aq_fetch_err")
+        return e.err_abs, e.err_signed
+
+    def integrate_batch_err(self, a, b, eps, integrand=COSH4, theta=None):
+        """integrate_batch (or, with theta, integrate_batch_params) with the error estimate: (area, tasks, accepted,
+        err_abs, err_signed) per integral, in input order."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        n = a.size
+        t = self._err_theta(integrand, theta, n)
+        area = np.empty(n, np.float64)
+        tasks = np.empty(n, np.uint64)
+        acc = np.empty(n, np.uint64)
+        err_abs = np.empty(n, np.float64)
+        err_signed = np.empty(n, np.float64)
+        _check(self.L.aq_integrate_batch_err(self._h, n, _dp(a), _dp(b), None if t is None else _dp(t), float(eps),
+                                             integrand, _dp(area), _up(acc), _up(tasks), _dp(err_abs), _dp(err_signed)),
+               "aq_integrate_batch_err")
+        return area, tasks, acc, err_abs, err_signed
 
 
 class Group:

@@ -167,6 +167,17 @@ struct aq_ctx {
     double* d_bthsorted = nullptr;     // [2][btheta_rows][nparams] (k_batch_scatter_theta)
     double* h_btheta = nullptr;        // [btheta_hcap][nparams]
     size_t btheta_rows = 0, btheta_hcap = 0;
+    // error estimate (the ERR launches, aq_*_err), allocated by the first ERR call (ensure_err; the batch
+    // rings by the first aq_integrate_batch_err): the slots' two sums, and the batch front end's rows -- two
+    // chunks' {err_abs, err_signed} on the device and the pinned copy of the whole call
+    double* d_err = nullptr;           // [NSLOTS_ALL][2] = Σ|d|, Σd over the slot's accepted tasks
+    double* h_err = nullptr;           // pinned, one pair (aq_fetch_err)
+    bool err_dirty[NSLOTS_ALL] = {};   // slot's pair written since it was last zeroed
+    bool slot_err[NSLOTS_ALL] = {};    // slot's last launch was an ERR launch (beside slot_hist)
+    int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
+    double* d_berr = nullptr;          // [2][berr_rows][2]
+    double* h_berr = nullptr;          // [berr_hcap][2]
+    size_t berr_rows = 0, berr_hcap = 0;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_pre = nullptr;
     // eval buffers
     double* d_x = nullptr;
@@ -220,6 +231,11 @@ int ensure_clean(aq_ctx* c, int s, int k) {
         memset(c->dirty + s, 0, (size_t)k);
     }
     memset(c->parts_dirty + s, 0, (size_t)k);
+    // the slots' error sums (ERR launches): zero again before any launch into them
+    if (c->d_err && memchr(c->err_dirty + s, 1, (size_t)k)) {
+        AQ_HIP(hipMemsetAsync(c->d_err + 2 * (size_t)s, 0, 2 * sizeof(double) * (size_t)k, c->stream));
+        memset(c->err_dirty + s, 0, (size_t)k);
+    }
     return AQ_OK;
 }
 
@@ -248,6 +264,19 @@ const void* stream_kernel(Variant v) {
         case Variant::HEAP: return (const void*)k_stream<FID, HIST, false, false, NW, true>;
     }
     return nullptr;
+}
+
+// ... and of an ERR launch's plan: three instances per integrand, all without histograms and diagnostics at
+// ERR_NW waves per workgroup -- per-CU (the plan's PCU and LONE), plain, heap.
+template <int FID>
+const void* stream_kernel_err(Variant v) {
+    switch (v) {
+        case Variant::PCU:
+        case Variant::LONE: return (const void*)k_stream<FID, false, false, true, ERR_NW, false, true>;
+        case Variant::PLAIN: return (const void*)k_stream<FID, false, false, false, ERR_NW, false, true>;
+        case Variant::HEAP: return (const void*)k_stream<FID, false, false, false, ERR_NW, true, true>;
+        default: return nullptr;   // (an ERR plan names no DIAG variant)
+    }
 }
 
 // Kernel timing (aq_kernel_timing / aq_kernel_time): a launch's event pair, reused from the free list, its
@@ -280,8 +309,10 @@ int timing_end(aq_ctx* ctx, const EventPair& ev) {
 template <int FID, bool HIST>
 int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const int32_t* shard_of, double eps,
                   int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
-                  const double* theta = nullptr, const double* dev_theta = nullptr) {
+                  const double* theta = nullptr, const double* dev_theta = nullptr, bool err = false) {
     static_assert(FID >= 0 && FID < 4, "aq_ctx::occ holds one row per integrand");
+    // err: an ERR launch (its instances keep no histograms: the callers pass HIST = false); ctx->d_err exists
+    if (err && (HIST || !ctx->d_err)) return AQ_EINVAL;
     // F_PARAM: the k parameter rows, on the host (staged and copied here, per-CU launches too: theta is
     // not a kernel argument) or already on the device in the launch's order (the batch front end)
     constexpr int NP = param::nparams;
@@ -289,18 +320,19 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     if (FID == F_PARAM && !theta && !dev_theta) return AQ_EINVAL;
     const int G = ctx->grid;
     const LaunchRequest rq{FID, G, k, shard_of != nullptr, nshards, first_slot, ctx->d_diag != nullptr,
-                           ctx->batch_heap, ctx->gsplit_env, eps};
+                           ctx->batch_heap, ctx->gsplit_env, eps, err};
     const LaunchPlan plan = plan_launch(rq, ctx->hint);
     if (plan.rc) return plan.rc;   // refused before anything is enqueued
     // per-CU launches pass their bounds as kernel arguments: no staging copy
     const bool pcu = plan.per_cu != 0;
-    const void* kfn = stream_kernel<FID, HIST>(plan.variant);
+    const void* kfn = plan.err ? stream_kernel_err<FID>(plan.variant) : stream_kernel<FID, HIST>(plan.variant);
+    if (!kfn) return AQ_EINVAL;
     // Co-residency (VERDICT r3 #6): idle workgroups wait on the HBM queue for busy ones, so the whole
     // grid must be resident at once. The device's answer for this exact instance (its VGPRs, its
     // static LDS, PT threads) times the CUs must cover the grid -- checked before anything is
     // enqueued, refused with a code instead of a stall. (Other kernels sharing the device, e.g. RCCL's,
     // can still delay some workgroups' start; the no-progress stall bound then ends the launch.)
-    int& occ = ctx->occ[FID][HIST][(int)plan.variant];
+    int& occ = plan.err ? ctx->occ_err[FID][(int)plan.variant] : ctx->occ[FID][HIST][(int)plan.variant];
     if (occ == 0) {
         AQ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, plan.nwt * 64, 0));
         if (occ < 1) occ = -1;
@@ -354,7 +386,8 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     P.q_next = ctx->d_q + (ctx->qsel ^ 1);
     P.parts = ctx->d_parts + 2 * parts_row(first_slot) * ctx->grid;
     P.parea = ctx->d_parea + 2 * parts_row(first_slot) * ctx->grid;
-    P.diag = ctx->d_diag;
+    if (plan.err) P.err = ctx->d_err;   // (shares diag's word: an ERR launch runs no DIAG instance)
+    else P.diag = ctx->d_diag;
     P.cu_acc = ctx->d_cu_acc;
     P.chunks = ctx->d_chunks;
     P.cellar = ctx->d_cellar;
@@ -386,13 +419,19 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     memset(ctx->dirty + first_slot, 1, (size_t)k);
     if (pcu) memset(ctx->parts_dirty + first_slot, 1, (size_t)k);
     memset(ctx->slot_hist + first_slot, HIST ? 1 : 0, (size_t)k);
+    memset(ctx->slot_err + first_slot, plan.err ? 1 : 0, (size_t)k);
+    if (plan.err) memset(ctx->err_dirty + first_slot, 1, (size_t)k);
     return AQ_OK;
 }
 
 int launch_any(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const int32_t* shard_of,
-               double eps, int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr) {
+               double eps, int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
+               bool err = false) {
     return with_fid(integrand, [&](auto F) {
         constexpr int FID = decltype(F)::value;
+        if (err)
+            return launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds,
+                                             nullptr, nullptr, true);
         return ctx->histograms
             ? launch_stream<FID, true>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds)
             : launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds);
@@ -408,13 +447,25 @@ int ensure_params(aq_ctx* ctx) {
     return dmalloc(ctx, &ctx->d_theta, sizeof(double) * NP * NSLOTS_ALL, false);
 }
 
+// The error estimate's slot sums, on the first ERR call (a fresh context and the plain calls hold none of
+// them: aq_ctx_device_bytes does not move until then). Zeroed once; ensure_clean and the readers keep the
+// slots zero between launches.
+int ensure_err(aq_ctx* ctx) {
+    if (ctx->d_err) return AQ_OK;
+    if (!ctx->h_err) AQ_HIP(hipHostMalloc(&ctx->h_err, 2 * sizeof(double), hipHostMallocDefault));
+    return dmalloc(ctx, &ctx->d_err, 2 * sizeof(double) * NSLOTS_ALL, true);
+}
+
 // launch_any for AQ_F_PARAM (with_fid stays the three fixed integrands': no level or frontier kernel
 // is instantiated for id 3)
 int launch_params(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta, double eps, int max_depth,
                   int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
-                  const double* dev_theta = nullptr) {
+                  const double* dev_theta = nullptr, bool err = false) {
     const int rc = ensure_params(ctx);
     if (rc) return rc;
+    if (err)
+        return launch_stream<F_PARAM, false>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
+                                             theta, dev_theta, true);
     return ctx->histograms
         ? launch_stream<F_PARAM, true>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
                                        theta, dev_theta)
@@ -517,9 +568,14 @@ static bool wait_sync_seq(aq_ctx* ctx, unsigned long long want) {
 // The synchronous calls' read-back of SYNC_SLOT: one k_fetch_sync launch writes the result into
 // pinned host memory and zeroes the slot; the host waits for its sequence number there
 // (AQ_SYNC_SPIN; 0: a stream synchronisation).
-static int fetch_sync(aq_ctx* ctx, aq_result* out) {
+// err: the call was an ERR launch -- its two sums come back in the same pinned result (SyncOut::err, written by
+// k_fetch_sync_err just ahead) and are zeroed too.
+static int fetch_sync(aq_ctx* ctx, aq_result* out, aq_err* err = nullptr) {
     const bool wp = ctx->parts_dirty[SYNC_SLOT], wh = ctx->slot_hist[SYNC_SLOT];
     const unsigned long long seq = ++ctx->sync_seq;
+    if (err)   // the two sums first: in the pinned result before k_fetch_sync releases the sequence number
+        hipLaunchKernelGGL(k_fetch_sync_err, dim3(1), dim3(64), 0, ctx->stream, ctx->d_err + 2 * (size_t)SYNC_SLOT,
+                           ctx->d_sync);
     hipLaunchKernelGGL(k_fetch_sync, dim3(1), dim3(256), 0, ctx->stream, ctx->d_ctl + SYNC_SLOT,
                        ctx->d_parts + 2 * parts_row(SYNC_SLOT) * ctx->grid,
                        (const double*)(ctx->d_parea + 2 * parts_row(SYNC_SLOT) * ctx->grid), ctx->grid, wp ? 1 : 0,
@@ -535,6 +591,11 @@ static int fetch_sync(aq_ctx* ctx, aq_result* out) {
     }
     ctx->dirty[SYNC_SLOT] = ctx->parts_dirty[SYNC_SLOT] = ctx->slot_hist[SYNC_SLOT] = false;
     const SyncOut& o = *ctx->h_sync;
+    if (err) {
+        ctx->err_dirty[SYNC_SLOT] = ctx->slot_err[SYNC_SLOT] = false;
+        err->err_abs = o.err[0];
+        err->err_signed = o.err[1];
+    }
     return finish_fetch(ctx, o.sums, o.area, wp ? o.parts : nullptr, wh ? o.hist : nullptr, out);
 }
 
@@ -739,6 +800,10 @@ void aq_ctx_destroy(aq_ctx* c) {
     (void)hipFree(c->d_bcnt);
     (void)hipFree(c->d_best);
     (void)hipFree(c->d_theta);
+    (void)hipFree(c->d_err);
+    (void)hipFree(c->d_berr);
+    if (c->h_err) (void)hipHostFree(c->h_err);
+    if (c->h_berr) (void)hipHostFree(c->h_berr);
     (void)hipFree(c->d_btheta);
     (void)hipFree(c->d_bthsorted);
     if (c->h_theta) (void)hipHostFree(c->h_theta);
@@ -972,6 +1037,67 @@ int aq_integrate_params(aq_ctx* ctx, const aq_problem* p, const double* theta, a
     if (rc) return rc;
     return fetch_sync(ctx, res);
 }
+
+// ---- error estimate (the ERR launches) -----------------------------------------------------------------
+double aq_err_extrapolate(double area, const aq_err* e) { return e ? area + e->err_signed / 3.0 : area; }
+
+// theta goes with AQ_F_PARAM and with nothing else
+static bool err_theta_ok(int integrand, const double* theta) {
+    return integrand == AQ_F_PARAM ? theta != nullptr : (integrand_ok(integrand) && theta == nullptr);
+}
+
+static int many_err_common(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const double* theta,
+                           double eps, int max_depth, int shard, int nshards, int first_slot, int slot_limit = NSLOTS) {
+    if (!ctx || k < 1 || k > MAXK || !a || !b) return AQ_EINVAL;
+    if (!err_theta_ok(integrand, theta)) return AQ_EINVAL;
+    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
+    if (nshards < 1 || nshards > 64 || shard < 0 || shard >= nshards) return AQ_EINVAL;
+    if (first_slot < 0 || first_slot + k > slot_limit) return AQ_EINVAL;
+    for (int i = 0; i < k; ++i)
+        if (theta ? !params_ok(a[i], b[i], theta + (size_t)i * param::nparams) : !bounds_ok(integrand, a[i], b[i]))
+            return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const int rc = ensure_err(ctx);
+    if (rc) return rc;
+    return theta ? launch_params(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot, nullptr, nullptr, true)
+                 : launch_any(ctx, integrand, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, nullptr, true);
+}
+
+int aq_integrate_many_err_async(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const double* theta,
+                                double eps, int max_depth, int shard, int nshards, int first_slot) {
+    return many_err_common(ctx, integrand, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+}
+
+int aq_integrate_err(aq_ctx* ctx, const aq_problem* p, const double* theta, aq_result* res, aq_err* err) {
+    if (!ctx || !p || !res || !err) return AQ_EINVAL;
+    if (!err_theta_ok(p->integrand, theta) || p->n_gpus > 1) return AQ_EINVAL;
+    if (!theta) {
+        const int rc = validate(p);
+        if (rc) return rc;
+    } else if (p->n_gpus < 0) {
+        return AQ_EINVAL;
+    }
+    ctx->sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
+    const int rc = many_err_common(ctx, p->integrand, 1, &p->a, &p->b, theta, p->eps, p->max_depth, 0, 1, SYNC_SLOT,
+                                   NSLOTS_ALL);
+    ctx->sync_fold = false;
+    if (rc) return rc;
+    return fetch_sync(ctx, res, err);
+}
+
+int aq_fetch_err(aq_ctx* ctx, int slot, aq_err* err) {
+    if (!ctx || !err || slot < 0 || slot >= NSLOTS) return AQ_EINVAL;
+    if (!ctx->d_err || !ctx->slot_err[slot]) return AQ_EINVAL;   // the slot's last launch was no ERR launch
+    AQ_HIP(hipSetDevice(ctx->device));
+    AQ_HIP(hipMemcpyAsync(ctx->h_err, ctx->d_err + 2 * (size_t)slot, 2 * sizeof(double), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    err->err_abs = ctx->h_err[0];
+    err->err_signed = ctx->h_err[1];
+    return AQ_OK;
+}
+
+// (aq_integrate_batch_err: beside the batch front end, below)
 
 // ---- RCCL group ----------------------------------------------------------------------------------
 int aq_group_unique_id(void* id) {
@@ -1398,8 +1524,12 @@ static void host_parallel(aq_ctx* ctx, size_t n, size_t grain, F&& f) {
 // theta: the parametrised family's rows [n][nparams] (integrand AQ_F_PARAM, aq_integrate_batch_params), else
 // null. The rows travel with the bounds: checked and staged with them, copied by the same stream into
 // their own device ring, carried into size order behind k_batch_scatter (k_batch_scatter_theta).
+// err: the ERR form (aq_integrate_batch_err) -- every chunk is an ERR launch, and its slots' error sums follow
+// the rows: gathered behind them in the same order (k_gather_err), copied back by the same stream, unpacked
+// with them into err_abs / err_signed (either may be null).
 static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
-                     int integrand, double* area, uint64_t* accepted, uint64_t* tasks) {
+                     int integrand, double* area, uint64_t* accepted, uint64_t* tasks, bool err = false,
+                     double* err_abs = nullptr, double* err_signed = nullptr) {
     // Batch front end (SURVEY config 3): up to MAXK integrals per persistent launch, every integral
     // with its own slot. Three streams (r05; profiles/r05a/c3_timeline_r04code.json had the launches
     // wait ~0.5 ms per chunk for a reset, a bounds copy, a full-width gather and a rows copy):
@@ -1486,6 +1616,24 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
             ctx->btheta_hcap = n;
         }
     }
+    if (err) {
+        if ((rc = ensure_err(ctx))) return rc;
+        if (ctx->berr_rows < rows) {
+            if (ctx->d_berr) { (void)hipFree(ctx->d_berr); ctx->dev_bytes -= sizeof(double) * 4 * ctx->berr_rows; }
+            ctx->d_berr = nullptr;
+            ctx->berr_rows = 0;
+            if ((rc = dmalloc(ctx, &ctx->d_berr, sizeof(double) * 4 * rows, false))) return rc;
+            ctx->berr_rows = rows;
+        }
+        if (ctx->berr_hcap < n) {
+            if (ctx->h_berr) AQ_HIP(hipHostFree(ctx->h_berr));
+            ctx->h_berr = nullptr;
+            ctx->berr_hcap = 0;
+            AQ_HIP(hipHostMalloc(&ctx->h_berr, sizeof(double) * 2 * n, hipHostMallocDefault));
+            ctx->berr_hcap = n;
+        }
+    }
+    auto dev_err_rows_of = [&](size_t c) { return ctx->d_berr + 2 * (c & 1u) * ctx->berr_rows; };
     const size_t RT = ctx->btheta_rows;
     auto dev_theta_of = [&](size_t c) { return ctx->d_btheta + (c & 1u) * RT * NP; };
     auto thsorted_of = [&](size_t c) { return ctx->d_bthsorted + (c & 1u) * RT * NP; };
@@ -1534,6 +1682,8 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
             if (tasks) tasks[i] = (uint64_t)row[1];
             if (accepted) accepted[i] = (uint64_t)row[2];
             e |= (unsigned)row[3];
+            if (err_abs) err_abs[i] = ctx->h_berr[2 * i];
+            if (err_signed) err_signed[i] = ctx->h_berr[2 * i + 1];
         }
         return e;
     };
@@ -1650,9 +1800,9 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
         ctx->batch_heap = true;
         rc = par ? launch_params(ctx, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
                                  sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c),
-                                 sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c))
+                                 sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c), err)
                  : launch_any(ctx, integrand, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
-                              sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c));
+                              sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c), err);
         ctx->batch_heap = false;
         ctx->hint.preset = false;
         mark("launched", (long)c);
@@ -1661,10 +1811,14 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
         if (c >= 2 && hipStreamWaitEvent(ctx->stream, ev_d2h(c - 2), 0) != hipSuccess) { rc = AQ_EHIP; break; }
         hipLaunchKernelGGL(k_gather_reset, dim3((m + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts,
                            ctx->grid, 0, m, dev_rows_of(c), sorted_chunk[c] ? perm_of(c) : nullptr);
+        if (err)   // (its rows' ring slot is free as the rows' is: the wait for chunk c - 2's copy above)
+            hipLaunchKernelGGL(k_gather_err, dim3((m + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, m,
+                               dev_err_rows_of(c), sorted_chunk[c] ? perm_of(c) : nullptr);
         if (hipGetLastError() != hipSuccess || hipEventRecord(ev_gath(c), ctx->stream) != hipSuccess) {
             rc = AQ_EHIP;
             break;
         }
+        if (err) memset(ctx->err_dirty, 0, (size_t)m);   // k_gather_err zeroed them
         memset(ctx->dirty, 0, (size_t)m);   // k_gather_reset zeroed them
         memset(ctx->parts_dirty, 0, (size_t)m);
         ++ran;
@@ -1676,6 +1830,8 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
         if (hipStreamWaitEvent(d2h_stream(c), ev_gath(c), 0) != hipSuccess ||
             hipMemcpyAsync(ctx->h_batch + 4 * off[c], dev_rows_of(c), sizeof(double) * 4 * (size_t)m,
                            hipMemcpyDeviceToHost, d2h_stream(c)) != hipSuccess ||
+            (err && hipMemcpyAsync(ctx->h_berr + 2 * off[c], dev_err_rows_of(c), sizeof(double) * 2 * (size_t)m,
+                                   hipMemcpyDeviceToHost, d2h_stream(c)) != hipSuccess) ||
             hipEventRecord(ev_d2h(c), d2h_stream(c)) != hipSuccess) {
             rc = AQ_EHIP;
             break;
@@ -1717,6 +1873,13 @@ int aq_integrate_batch_params(aq_ctx* ctx, size_t n, const double* a, const doub
                               double* area, uint64_t* accepted, uint64_t* tasks) {
     if (!ctx || !theta) return AQ_EINVAL;
     return batch_run(ctx, n, a, b, theta, eps, AQ_F_PARAM, area, accepted, tasks);
+}
+
+int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
+                           int integrand, double* area, uint64_t* accepted, uint64_t* tasks, double* err_abs,
+                           double* err_signed) {
+    if (!ctx || !err_theta_ok(integrand, theta)) return AQ_EINVAL;
+    return batch_run(ctx, n, a, b, theta, eps, integrand, area, accepted, tasks, true, err_abs, err_signed);
 }
 
 int aq_frontier_root(aq_ctx* ctx, int integrand, double a, double b, double* d_out) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "aquad.h"
 #include "aq_libm.h"
 
@@ -79,6 +81,14 @@ struct Step2 {
     double fmid, area2;   // F(mid) and 2 * (larea + rarea)
     bool refine;
 };
+// The ERR instances' step (k_stream ERR): Step2 and the difference the refine test of :191 takes the
+// magnitude of, `diff` = area2 - lr2 (doubled areas: 2 f_scale d, exact) or (larea + rarea) - lrarea = d
+// itself (plug-in integrands) -- the per-leaf term of the error estimate, with no extra operation.
+struct Step2e : Step2 {
+    double diff;
+};
+template <typename S>
+constexpr bool step_has_diff = std::is_same<S, Step2e>::value;
 //
 // Doubling needs every product to stay normal: the built-in integrands guarantee it on their
 // validated domains (aq_abi.inc bounds_ok). A plug-in F (F_USER, F_PARAM) can be anything, so its trees use
@@ -96,10 +106,10 @@ __host__ __device__ constexpr double f_scale() { return FID == F_COSH4 ? 16.0 : 
 template <int FID>
 __host__ __device__ constexpr double area_scale() { return doubled_areas<FID>() ? 0.5 / f_scale<FID>() : 1.0; }
 
-template <int FID, int K>
+template <int FID, int K, typename S = Step2>
 __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (&r)[K], const double (&fl)[K],
                                             const double (&fr)[K], double eps2, const ExpEntry* __restrict__ tab,
-                                            Step2 (&s)[K], const ExpConsts& kk = ExpConsts{}, int range_hint = -1,
+                                            S (&s)[K], const ExpConsts& kk = ExpConsts{}, int range_hint = -1,
                                             unsigned long long out_mask = 0ull, const Theta<FID>& th = Theta<FID>{}) {
     double mid[K], fmid[K];
 #pragma unroll
@@ -125,6 +135,7 @@ __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (
             s[k].fmid = fmid[k];
             s[k].area2 = l2 + r2;
             s[k].refine = fabs(s[k].area2 - lr2) > eps2;                  // :191 (strict >)
+            if constexpr (step_has_diff<S>) s[k].diff = s[k].area2 - lr2;
         } else {   // eps2 is eps here (area_scale 1)
             const double lrarea = (fl[k] + fr[k]) * (r[k] - l[k]) / 2;    // :185
             const double larea = (fl[k] + fmid[k]) * (mid[k] - l[k]) / 2; // :189
@@ -132,6 +143,7 @@ __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (
             s[k].fmid = fmid[k];
             s[k].area2 = larea + rarea;                                   // :199
             s[k].refine = fabs((larea + rarea) - lrarea) > eps2;          // :191 (strict >)
+            if constexpr (step_has_diff<S>) s[k].diff = (larea + rarea) - lrarea;
         }
     }
 }
@@ -145,9 +157,9 @@ __device__ __forceinline__ void task_step_k(const double (&l)[K], const double (
 // the widths of :189 / :190 -- the reference's values, one operation each, so the three midpoints
 // cost three adds and one multiply where (l + r) / 2 costs an add and a multiply each. The
 // children pairs are {ha, hm} and {hm, hb}: already at hand. Returns m and hm for the pushes.
-template <int FID, unsigned TABMASK = 127u>
+template <int FID, unsigned TABMASK = 127u, typename S = Step2>
 __device__ __forceinline__ void pair_step_halves(double ha, double hb, double fa, double fm, double fb, double eps2,
-                                                 const ExpEntry* __restrict__ tab, Step2 (&s)[2], double& m,
+                                                 const ExpEntry* __restrict__ tab, S (&s)[2], double& m,
                                                  double& hm, const ExpConsts& kk, int range_hint,
                                                  unsigned long long out_mask, const Theta<FID>& th = Theta<FID>{}) {
     m = ha + hb;                                             // the parent's midpoint (:187)
@@ -174,12 +186,14 @@ __device__ __forceinline__ void pair_step_halves(double ha, double hb, double fa
             const double r2 = (fmid[k] + fr[k]) * wr[k];     // 2 * rarea, :190
             s[k].area2 = l2 + r2;
             s[k].refine = fabs(s[k].area2 - lr2e[k]) > eps2;   // :191 (strict >)
+            if constexpr (step_has_diff<S>) s[k].diff = s[k].area2 - lr2e[k];
         } else {
             const double lrarea = lr2e[k] / 2;                // :185
             const double larea = (fl[k] + fmid[k]) * wl[k] / 2;   // :189
             const double rarea = (fmid[k] + fr[k]) * wr[k] / 2;   // :190
             s[k].area2 = larea + rarea;                       // :199
             s[k].refine = fabs((larea + rarea) - lrarea) > eps2;   // :191
+            if constexpr (step_has_diff<S>) s[k].diff = (larea + rarea) - lrarea;
         }
     }
 }
@@ -285,6 +299,23 @@ __device__ __forceinline__ void masked_acc3(double& hi, double a0, unsigned long
         : "v"(a0), "v"(a1), "s"(l0m), "s"(l1m), "s"(am), "v"(v));
 }
 
+// The ERR round's four masked accumulations in one exec window: sg += d0, ab += |d0| on the lanes of l0m,
+// then d1 on l1m -- one exec-masked v_add_f64 per sum and accepted task, the magnitude a source modifier.
+__device__ __forceinline__ void masked_err4(double& sg, double& ab, double d0, unsigned long long l0m, double d1,
+                                            unsigned long long l1m) {
+    unsigned long long saved;
+    asm("s_mov_b64 %2, exec\n\t"
+        "s_mov_b64 exec, %5\n\t"
+        "v_add_f64 %0, %0, %3\n\t"
+        "v_add_f64 %1, %1, |%3|\n\t"
+        "s_mov_b64 exec, %6\n\t"
+        "v_add_f64 %0, %0, %4\n\t"
+        "v_add_f64 %1, %1, |%4|\n\t"
+        "s_mov_b64 exec, %2"
+        : "+v"(sg), "+v"(ab), "=&s"(saved)
+        : "v"(d0), "v"(d1), "s"(l0m), "s"(l1m));
+}
+
 __device__ __forceinline__ void wave_sum_dd(double& hi, double& lo) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -330,6 +361,14 @@ __device__ __forceinline__ unsigned wave_max_full(unsigned v) {
 }
 __device__ __forceinline__ unsigned wave_or_full(unsigned v) {
     return wave_reduce_u(v, [](unsigned x, unsigned y) { return x | y; });
+}
+// plain double sum over the wave (every lane active); the result is wave-uniform
+__device__ __forceinline__ double wave_sum_d_full(double v) {
+    v += dpp_d<DPP_XOR1>(v);
+    v += dpp_d<DPP_XOR2>(v);
+    v += dpp_d<DPP_HALF_MIRROR>(v);
+    v += dpp_d<DPP_MIRROR>(v);
+    return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
 }
 // double-double sum over each row of 16 lanes (every lane active): every lane holds its row's sum
 __device__ __forceinline__ void row_sum_dd(double& hi, double& lo) {

@@ -22,7 +22,14 @@ struct LaunchRequest {
     bool batch_heap = false;   // a batch front end's launch
     int gsplit_env = 0;        // AQ_GSPLIT: waves per job of a multi-integral launch (0 = default)
     double eps = 0.0;
+    bool err = false;          // an ERR launch: the error estimate's sums beside the area (k_stream ERR)
 };
+
+// Waves per workgroup of every ERR launch, whatever its shape (two per SIMD: the ERR instances' registers,
+// aq_stream.h k_stream). One value for all of them, so every ERR launch of one nshards deals the same
+// partition and an integral's shards add up; the counts do not depend on the partition.
+constexpr int ERR_NW = 8;
+static_assert(ERR_NW <= NW && ERR_NW % 4 == 0, "whole waves per SIMD, within the LDS rings");
 
 // The workload the device's job-size hint (LaunchHint) was measured on, as the host knows it.
 struct HintState {
@@ -44,6 +51,8 @@ struct LaunchPlan {
     int tail_from = 0, tail_mult = 1;
     int per_cu = 0, static_jobs = 0, adaptive = 0;
     HintState hint;            // the hint state after the launch
+    bool err = false;          // the request's ERR flag: the variant's ERR instance runs (PCU, LONE -> the per-CU
+                               // one; PLAIN; HEAP), without diagnostics
 };
 
 // seeding keeps F and flags of every path node of a share in the wave's ring: (D + 1) levels x
@@ -69,15 +78,18 @@ inline LaunchPlan plan_launch(const LaunchRequest& r, const HintState& hint) {
     // 69.3 us against 67.3 at 12, profiles/r05k)
     // (one integral only, k == 1: the measured case and the partition include/aquad.h documents; launches
     // of 2-11 integrals keep NW)
-    const bool lone = !sin_recip && AQ_LONE_NW != NW && pcu && !r.diag && unsharded && k == 1;
-    p.nwt = lone ? AQ_LONE_NW : NW;
+    // (ERR launches run no diagnostics instance)
+    const bool diag = r.diag && !r.err;
+    const bool lone = !sin_recip && AQ_LONE_NW != NW && pcu && !diag && unsharded && k == 1;
+    p.nwt = r.err ? ERR_NW : lone ? AQ_LONE_NW : NW;
+    p.err = r.err;
     const int W = r.grid * p.nwt;
     // the batch front end's multi-integral launches and unsharded launches of fewer integrals than waves:
     // the instance with heap-order seeding of whole-integral jobs and up to one job per wave (aq_stream.h
     // HEAPS, MIN_JOB_TASKS)
-    const bool heap = !pcu && !r.diag && (r.batch_heap || (k < W && unsharded));
+    const bool heap = !pcu && !diag && (r.batch_heap || (k < W && unsharded));
     p.variant = heap ? Variant::HEAP : lone ? Variant::LONE
-              : r.diag ? (pcu ? Variant::DIAG_PCU : Variant::DIAG) : (pcu ? Variant::PCU : Variant::PLAIN);
+              : diag ? (pcu ? Variant::DIAG_PCU : Variant::DIAG) : (pcu ? Variant::PCU : Variant::PLAIN);
     // jobs: one integral is split into one share per wave (the partition the oracle restates); a
     // multi-integral launch uses gsplit-times larger shares, so one seeding pass feeds more rounds.
     // A shard of N holds 1/N of each integral: its shares are N times fewer, so a job (and its

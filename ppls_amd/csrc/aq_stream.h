@@ -404,7 +404,14 @@ struct StreamParams {
                                     // [2 * (p * gridDim.x + wg) + 0/1] (the first slot's parts row)
     double* parea;                  // ... and their area, a double-double per workgroup at [2 * (p * gridDim.x
                                     // + wg) + 0/1] (the same row of the area words; PCU_AREA)
-    unsigned long long* diag;       // optional per-workgroup timeline (DIAG_WORDS each)
+    union {
+        unsigned long long* diag;   // optional per-workgroup timeline (DIAG_WORDS each)
+        double* err;                // ERR instances (which keep no diagnostics): the slots' error sums, slot s at
+                                    // [2 * s + 0/1] = Σ|d|, Σd over its accepted tasks (d = (larea + rarea) - lrarea,
+                                    // :191). It shares diag's word: the block is full to its 16-byte alignment, and
+                                    // a field more moves the hidden kernel arguments behind it -- a changed load
+                                    // offset in every existing instance
+    };
     unsigned long long* cu_acc;     // [AQ_CU_SLOTS] tasks per hardware CU slot, summed over launches
                                     // (every launch: the farmer's tasks_per_process, :162, per CU)
     Chunk* chunks;
@@ -420,6 +427,7 @@ struct StreamParams {
     const double* theta;            // F_PARAM: [nprob][param::nparams] row-major, integral p's row at p * nparams
                                     // (device memory, written before the launch; else null)
 };
+static_assert(sizeof(StreamParams) == 384, "the kernels' hidden arguments follow the block: a larger one moves them in every instance");
 
 // Diagnostics record per workgroup (aq_set_diagnostics), accumulated in LDS by every wave:
 // realtime stamps are s_memrealtime ticks (100 MHz), cycle counts are s_memtime shader cycles.
@@ -511,6 +519,17 @@ struct Acc {
                                     // let two schedules of one batch differ by > 2 ulp)
 };
 
+// The ERR instances' per-lane sums over the accepted tasks of the integral being summed (`tag`): the
+// signed and the absolute sum of the differences the refine test measures (Step2e::diff; doubled areas of
+// f_scale F for the built-in integrands, scaled by area_scale at the flush as the area is). Plain doubles:
+// the estimate needs no exact accumulator. The other instances' is empty.
+template <bool ERR>
+struct ErrAcc {};
+template <>
+struct ErrAcc<true> {
+    double sg = 0.0, ab = 0.0;
+};
+
 // Flush a wave's accumulators for integral `tag` and reset them: the wave's double-double area (hi
 // and lo, each exact) into the integral's exact accumulator; the counts into the slot sums (device
 // atomics, spread over the launch's integrals), or -- per-CU launches, where every wave works on the
@@ -518,10 +537,14 @@ struct Acc {
 // slot once per workgroup at exit (3072 waves would otherwise queue on one slot's lines).
 // pc: the per-CU instance's LDS counts, [0,16) tasks, [16,32) accepted, [32,48) levels per integral;
 // px: its LDS accumulators, one XSum per integral.
-template <int FID, bool PCU>
+// ERR: the wave's two error sums go with them -- folded across the wave (DPP, plain doubles) wherever this
+// runs, so at every integral switch too -- into the slot's pair of P.err with FP64 device atomics by lane
+// 0, or (per-CU) into the wave's own LDS pair of the integral, werr[tag * wdd_stride] = {Σ|d|, Σd}, which
+// the workgroup's last wave adds to the slot once per integral at exit.
+template <int FID, bool PCU, bool ERR = false>
 __device__ __forceinline__ void flush_acc(const StreamParams& P, Acc& a, int tag, unsigned lane, WgState& S,
                                           unsigned long long* pc, double2* wdd, int wdd_stride, long long* xsa,
-                                          long long* xsb) {
+                                          long long* xsb, ErrAcc<ERR>& ea, double2* werr) {
     // (the rounds' lane partial is folded at every burst's end; fold any remainder here too)
     dd_add(a.hi, a.lo, a.r);
     a.r = 0.0;
@@ -579,6 +602,19 @@ __device__ __forceinline__ void flush_acc(const StreamParams& P, Acc& a, int tag
                 }
             }
         }
+        if constexpr (ERR) {
+            const double eab = area_scale<FID>() * wave_sum_d_full(ea.ab), esg = area_scale<FID>() * wave_sum_d_full(ea.sg);
+            if (lane == 0 && t) {
+                if constexpr (PCU) {
+                    double2& w = werr[tag * wdd_stride];
+                    w = make_double2(w.x + eab, w.y + esg);
+                } else {
+                    double* e = P.err + 2 * (size_t)(P.first_slot + tag);
+                    unsafeAtomicAdd(e, eab);
+                    unsafeAtomicAdd(e + 1, esg);
+                }
+            }
+        }
         if (AQ_FLUSHX != 2 && lane == 0 && t) {
             atomicAdd(&S.tasks, (unsigned long long)t);
             if constexpr (PCU) {
@@ -608,6 +644,7 @@ __device__ __forceinline__ void flush_acc(const StreamParams& P, Acc& a, int tag
     a.tasks = a.leaves = a.maxd = 0;
     a.ut = a.ul = 0;
     a.maxdt = 0;
+    if constexpr (ERR) ea.sg = ea.ab = 0.0;
     __builtin_amdgcn_wave_barrier();   // reconverge: keeps the caller's wave state out of this join
 }
 
@@ -761,8 +798,12 @@ __device__ unsigned long long g_aq_stamps[MAXG * NW * ST_STRIDE];
 // NWT: waves per workgroup -- NW (12: three per SIMD) for every launch but the unsharded lone ones,
 // which run AQ_LONE_NW (aq_launch_plan.h plan_launch): a lone integral's set-up and seeding are VALU-bound
 // at three waves per SIMD, and its rounds are bound by one wave's heaviest share.
-template <int FID, bool HIST, bool DIAG, bool PCU, int NWT = NW, bool HEAPS = false>
+// ERR: the launch also sums the error estimate's two terms per integral (ErrAcc, flush_acc). Its instances
+// run without histograms and diagnostics at ERR_NW waves per workgroup (aq_launch_plan.h): the two sums and
+// the differences they add would not fit the 168 VGPRs of three waves per SIMD beside the round's state.
+template <int FID, bool HIST, bool DIAG, bool PCU, int NWT = NW, bool HEAPS = false, bool ERR = false>
 __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
+    static_assert(!ERR || (!HIST && !DIAG), "ERR launches keep no histograms and no diagnostics");
     constexpr int PTT = NWT * 64;   // threads per workgroup
     static_assert(NWT >= 4 && NWT <= NW && NWT % 4 == 0, "whole waves per SIMD, within the LDS rings");
     static_assert(NWT <= 16, "the exit's area sum runs over one DPP row of lanes (PCU_AREA)");
@@ -791,6 +832,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
     __shared__ WgState S;
     __shared__ unsigned long long s_pc[PCU ? 3 * PCU_ROW : 1];
     __shared__ double2 s_wdd[PCU ? PCU_ROW * NWT : 1];   // per-CU launches: each wave's area per integral
+    __shared__ double2 s_werr[PCU && ERR ? PCU_ROW * NWT : 1];   // ... and (ERR) its error sums {Σ|d|, Σd}
     __shared__ unsigned long long s_dg[DIAG ? DIAG_WORDS : 1];
 
     const unsigned tid = threadIdx.x;
@@ -832,6 +874,8 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
     if (PCU && tid < 3u * PCU_ROW) s_pc[tid] = 0ull;
     if (PCU)
         for (unsigned i = tid; i < (unsigned)(PCU_ROW * NWT); i += PTT) s_wdd[i] = make_double2(0.0, 0.0);
+    if constexpr (PCU && ERR)
+        for (unsigned i = tid; i < (unsigned)(PCU_ROW * NWT); i += PTT) s_werr[i] = make_double2(0.0, 0.0);
     if (DIAG) {
         for (unsigned i = tid; i < DIAG_WORDS; i += PTT) s_dg[i] = (i == DG_T_FIRST_LEAD) ? ~0ull : 0ull;
     }
@@ -901,6 +945,14 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
     asm volatile("" : "+v"(ring_vmask));   // kept in a VGPR (see ring_addr)
 
     Acc acc{0.0, 0.0, 0u, 0u, 0u, 0u, 0u, 0u};
+    ErrAcc<ERR> eacc;             // ERR: the error sums of `tag` (flushed with acc)
+    // an accepted seeding task's difference d (:191), scaled like the rounds' (1 / area_scale: exact)
+    auto err_leaf = [&](double d) {
+        if constexpr (ERR) {
+            eacc.sg += d / area_scale<FID>();
+            eacc.ab += fabs(d) / area_scale<FID>();
+        }
+    };
     int tag = 0;                  // integral the accumulators belong to (wave-uniform)
     Theta<FID> th{};              // its parameter row (F_PARAM; wave-uniform), reloaded wherever tag is assigned
     sload_theta<FID>(th, P.theta, tag);
@@ -1126,7 +1178,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             }
             if (k) {
                 if (ptag != tag) {     // the ring's new integral
-                    flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
+                    flush_acc<FID, PCU, ERR>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b, eacc, s_werr + wid);
                     tag = ptag;
                     sload_theta<FID>(th, P.theta, tag);
                 }
@@ -1183,7 +1235,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                 unsigned long long cf0 = 0;
                 if constexpr (AQ_STAMPS && !DIAG) cf0 = clk();
                 if (p != tag) {
-                    flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
+                    flush_acc<FID, PCU, ERR>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b, eacc, s_werr + wid);
                     tag = p;
                     sload_theta<FID>(th, P.theta, tag);
                 }
@@ -1228,6 +1280,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                 double* fm = s_a + base;          // [nnodes + 2]: F(mid of (d,k)) at d*nb+k, then F(A), F(B)
                 double* leafa = s_b + base;       // [nnodes]: larea + rarea of node (d,k)
                 const DtField flag = s_dt + base;  // [nnodes]: node (d,k) refines
+                [[maybe_unused]] double* dleafa = s_fa + base;   // ERR [nnodes]: node (d,k)'s difference d (:191)
                 auto position = [&](unsigned kk, bool& valid) -> unsigned long long {
                     const unsigned long long o = (kk & 1u) ? (unsigned long long)(V - 1 - vw) : (unsigned long long)vw;
                     const unsigned long long j = (unsigned long long)kk * V + o;
@@ -1266,6 +1319,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     __builtin_amdgcn_wave_barrier();
                     bool refine = false;
                     double leafarea = 0.0;
+                    [[maybe_unused]] double dleaf = 0.0;   // ERR: the node's difference d (:191)
                     if (isnode) {
                         fl = fm[li];
                         fr = fm[ri];
@@ -1274,6 +1328,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                         const double rarea = (fmid + fr) * (r - mid) / 2;     // :190
                         refine = fabs((larea + rarea) - lrarea) > eps;       // :191
                         leafarea = larea + rarea;                             // :199
+                        if constexpr (ERR) dleaf = (larea + rarea) - lrarea;
                     }
                     // a node is a task of the tree iff every ancestor refines (:192-197)
                     const unsigned long long rm = __ballot(isnode && refine);
@@ -1289,6 +1344,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                         if (!refine) {
                             dd_add(acc.hi, acc.lo, leafarea / area_scale<FID>());   // :199 -> :149 (doubled, exact)
                             ++acc.leaves;
+                            err_leaf(dleaf);
                             if (HIST) atomicAdd(&P.ctls[P.first_slot + p].hist[AQ_MAX_LEVELS + d], 1ull);
                         } else if ((int)d + 1 >= max_depth) {
                             err |= ERRB_DEPTH;
@@ -1334,6 +1390,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     }
                     bool refine = false;
                     double leafarea = 0.0;
+                    [[maybe_unused]] double dleaf = 0.0;   // ERR: the node's difference d (:191)
                     if (isnode) {
                         fl = fm[li];
                         fr = fm[ri];
@@ -1342,6 +1399,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                         const double rarea = (fmid + fr) * (r - mid) / 2;     // :190
                         refine = fabs((larea + rarea) - lrarea) > eps;       // :191
                         leafarea = larea + rarea;                             // :199
+                        if constexpr (ERR) dleaf = (larea + rarea) - lrarea;
                     }
                     const unsigned long long leafm = __ballot(isnode && valid && !refine) & colmask;
                     const unsigned dstar = leafm ? (unsigned)__builtin_ctzll(leafm) / nb : nlev;
@@ -1352,6 +1410,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                         if (d == dstar) {
                             dd_add(acc.hi, acc.lo, leafarea / area_scale<FID>());   // :199 -> :149 (doubled, exact)
                             ++acc.leaves;
+                            err_leaf(dleaf);
                             if (HIST) atomicAdd(&P.ctls[P.first_slot + p].hist[AQ_MAX_LEVELS + d], 1ull);
                         } else if ((int)d + 1 >= max_depth) {
                             err |= ERRB_DEPTH;
@@ -1377,6 +1436,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     unsigned dd[2], kc[2], lix[2], rix[2];
                     unsigned long long ppx[2];
                     double lx[2], rx[2], mx[2], fx[2], flx[2], frx[2], lax[2];
+                    [[maybe_unused]] double dlx[2] = {0.0, 0.0};   // ERR: the nodes' differences d (:191)
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const unsigned q = lane + 64u * (unsigned)h;
@@ -1420,6 +1480,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                             const double rarea = (fx[h] + frx[h]) * (rx[h] - mx[h]) / 2;     // :190
                             rfn[h] = fabs((larea + rarea) - lrarea) > eps;                   // :191
                             lax[h] = larea + rarea;                                          // :199
+                            if constexpr (ERR) dlx[h] = (larea + rarea) - lrarea;
                         }
                     }
                     const unsigned long long lm_lo = __ballot(isn[0] && vld[0] && !rfn[0]);
@@ -1441,6 +1502,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                             if (d == dstar) {
                                 dd_add(acc.hi, acc.lo, lax[h] / area_scale<FID>());   // :199 -> :149
                                 ++acc.leaves;
+                                err_leaf(dlx[h]);
                                 if (HIST) atomicAdd(&P.ctls[P.first_slot + p].hist[AQ_MAX_LEVELS + d], 1ull);
                             } else if ((int)d + 1 >= max_depth) {
                                 err |= ERRB_DEPTH;
@@ -1495,6 +1557,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                             const double rarea = (fmd + frr) * (rr - mm) / 2;     // :190
                             flag[q] = fabs((larea + rarea) - lrarea) > eps ? 1u : 0u;   // :191
                             leafa[q] = larea + rarea;                             // :199
+                            if constexpr (ERR) dleafa[q] = (larea + rarea) - lrarea;
                         }
                     }
                     if constexpr (DIAG) cp2 = clk();
@@ -1516,6 +1579,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                                 if (d == dstar) {
                                     dd_add(acc.hi, acc.lo, leafa[d * nb + kk] / area_scale<FID>());   // :199 -> :149 (doubled)
                                     ++acc.leaves;
+                                    if constexpr (ERR) err_leaf(dleafa[d * nb + kk]);
                                     if (HIST) atomicAdd(&P.ctls[P.first_slot + p].hist[AQ_MAX_LEVELS + d], 1ull);
                                 } else if ((int)d + 1 >= max_depth) {
                                     err |= ERRB_DEPTH;
@@ -1593,7 +1657,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             // a wave that ran dry flushes now, off the run's critical path: the workgroup's other waves
             // while its last still works; the last one (the leader) once the end is stored or while it
             // waits, below (every wave flushing after the end was seen had cost a lone launch ~1 us, r04j)
-            if (counted_now) flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
+            if (counted_now) flush_acc<FID, PCU, ERR>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b, eacc, s_werr + wid);
             if (!lead) {
                 __builtin_amdgcn_s_sleep(4);
                 __builtin_amdgcn_wave_barrier();
@@ -1619,7 +1683,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             }
             // the leader's flush: behind the end's stores (the run's last leader: the other workgroups
             // see the end meanwhile), or before its wait
-            flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
+            flush_acc<FID, PCU, ERR>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b, eacc, s_werr + wid);
             if (lane == 0) {
                 if (!last) {
                     // per-CU launches: the end flag alone first (one load per spin, no ticket)
@@ -1905,14 +1969,15 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             const double pa = ca, pb = cb, pfa = cfa, pfm = cfm, pfb = cfb;
             const unsigned long long dtw = (unsigned long long)__double_as_longlong(cdw);
             const unsigned dt = (unsigned)dtw;
-            Step2 st[2];
+            using StepT = typename std::conditional<ERR, Step2e, Step2>::type;   // (ERR: with the difference of :191)
+            StepT st[2];
             // the lanes whose pair lacks SPAN_BIT (both midpoints lie in the pair's interval, so one
             // sign test of the pair word)
             unsigned long long nospan = 0ull;
             if constexpr (FID == F_COSH4) nospan = __ballot((int)dt >= 0);
             double pm, hm;
-            pair_step_halves<FID, WIDE ? 255u : 127u>(pa, pb, pfa, pfm, pfb, eps2, tab, st, pm, hm, kk,
-                                                       FID == F_COSH4 ? 2 : -1, nospan & am, th);
+            pair_step_halves<FID, WIDE ? 255u : 127u, StepT>(pa, pb, pfa, pfm, pfb, eps2, tab, st, pm, hm, kk,
+                                                              FID == F_COSH4 ? 2 : -1, nospan & am, th);
             if constexpr (prio_by_load) { if (!b_heavy) asm volatile("s_setprio 0"); }
             const unsigned long long r0m = __ballot(st[0].refine), r1m = __ballot(st[1].refine);
             unsigned long long okm = am;
@@ -1931,6 +1996,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             const unsigned long long cdtw = ((dtw >> 32) << 32) | (unsigned long long)cdt;
             masked_acc3(acc.r, st[0].area2, l0m, st[1].area2, l1m, acc.maxdt, burst_cap ? cdt : dt,
                         burst_cap ? (mask0 | mask1) : am);
+            if constexpr (ERR) masked_err4(eacc.sg, eacc.ab, st[0].diff, l0m, st[1].diff, l1m);
             if constexpr (DIAG) {
                 const int rtag = (int)dt_tag(dt);
                 b_mixed |= (__ballot(rtag != tag) & am) != 0ull;
@@ -2059,7 +2125,7 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
     // ---------------- exit: flush this wave's accumulators (no workgroup barrier needed) --------
     if constexpr (DIAG) { if (lane == 0) atomicMax(&s_dg[DG_T_BROKE], rtc()); }
     stamp(ST_BROKE);
-    flush_acc<FID, PCU>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b);
+    flush_acc<FID, PCU, ERR>(P, acc, tag, lane, S, s_pc, s_wdd + wid, NWT, xs_a, xs_b, eacc, s_werr + wid);
     if constexpr (DIAG) { if (lane == 0) atomicMax(&s_dg[DG_T_FLUSHED], rtc()); }
     stamp(ST_FLUSHED);
     if (mixed) err |= ERRB_OVERFLOW;
@@ -2145,6 +2211,22 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
                     double* pa = P.parea + 2 * ((size_t)p * gridDim.x + bid);
                     pa[0] = hi;
                     pa[1] = lo;
+                }
+                if constexpr (ERR) {
+                    // the waves' error sums of the integral, once per workgroup: two FP64 atomics into its slot
+                    if (lane == 0) {
+                        double eab = 0.0, esg = 0.0;
+                        for (int w = 0; w < NWT; ++w) {
+                            const double2 e = s_werr[p * NWT + w];
+                            eab += e.x;
+                            esg += e.y;
+                        }
+                        if (eab != 0.0) {
+                            double* e = P.err + 2 * (size_t)(P.first_slot + p);
+                            unsafeAtomicAdd(e, eab);
+                            unsafeAtomicAdd(e + 1, esg);
+                        }
+                    }
                 }
             }
         }

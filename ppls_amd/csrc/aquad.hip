@@ -713,6 +713,19 @@ __global__ __launch_bounds__(64) void k_gather_reset(Ctl* __restrict__ ctls, con
     c.sums = SlotSums{};
 }
 
+// The ERR batch's second gather (aq_integrate_batch_err), behind k_gather_reset: the slots' error sums as
+// rows {err_abs, err_signed} in the order k_gather_reset wrote its rows, and the sums back to zero.
+__global__ __launch_bounds__(64) void k_gather_err(double* __restrict__ err, int first, int n, double* __restrict__ out,
+                                                   const unsigned* __restrict__ perm) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    double* e = err + 2 * (size_t)(first + i);
+    double* o = out + 2 * (size_t)(perm ? perm[i] : (unsigned)i);
+    o[0] = e[0];
+    o[1] = e[1];
+    e[0] = e[1] = 0.0;
+}
+
 // The same slots as exact int64 rows (AQ_EXACT_ROW each): limbs, tasks, accepted, spilled,
 // levels | error << 32. Sums of such rows (an int64 all-reduce) keep the area exact.
 __global__ __launch_bounds__(64) void k_gather_exact(const Ctl* __restrict__ ctls,
@@ -785,6 +798,7 @@ struct SyncOut {
     XSum area;
     unsigned long long hist[2 * AQ_MAX_LEVELS];
     unsigned long long parts[2 * MAXG];
+    double err[2];            // ERR calls: the slot's error sums {Σ|d|, Σd} (aq_integrate_err)
 };
 __global__ __launch_bounds__(256) void k_fetch_sync(Ctl* __restrict__ c, unsigned long long* __restrict__ parts,
                                                     const double* __restrict__ parea, int grid, int with_parts,
@@ -814,6 +828,17 @@ __global__ __launch_bounds__(256) void k_fetch_sync(Ctl* __restrict__ c, unsigne
     __threadfence_system();
     __syncthreads();
     if (t == 0) __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// The ERR synchronous call (aq_integrate_err): the sync slot's pair of error sums (err: its two doubles) into
+// the pinned result and back to zero -- launched on the stream IN FRONT of k_fetch_sync, whose sequence
+// number the host waits for: this kernel has completed, its stores visible system-wide, before that one starts.
+__global__ __launch_bounds__(64) void k_fetch_sync_err(double* __restrict__ err, SyncOut* __restrict__ out) {
+    const int t = threadIdx.x;
+    if (t < 2) {
+        out->err[t] = err[t];
+        err[t] = 0.0;
+    }
+    __threadfence_system();
 }
 
 // aq_integrate_group: one rank's contribution to the RCCL exchange. sum_row (int64, summed over

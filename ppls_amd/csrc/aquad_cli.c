@@ -2,7 +2,7 @@
  * aquad_cli.c -- drop-in for `mpirun -n P ./aquadPartA` (/root/reference/aquadPartA.c main(), :78-123).
  *
  *   aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] [--theta v0,v1,...]
- *         [--per-cu] [--levels]
+ *         [--per-cu] [--levels] [--err]
  *
  * Same observable surface as the reference: `Area=%lf`, a blank line, `Tasks Per Process`, the index
  * row and the count row (tab-terminated entries). Process 0 is the farmer and always reports 0 tasks
@@ -14,6 +14,9 @@
  * GPU; aq_integrate_group combines the shards with one grouped all-reduce / all-gather).
  * `--f param --theta v0,v1,...` integrates the parametrised family F(x; theta) (aq_integrate_params; as many
  * values as aq_param_count(); one GPU). The printout is the same.
+ * `--err` (one GPU, no --levels) runs the error-estimate form (aq_integrate_err): the printout is unchanged,
+ * and two lines follow it, `Error estimate=%.6e` (the sum of |d| over the accepted intervals, d the
+ * difference the test at :191 bounds) and `Extrapolated area=%.17g` (aq_err_extrapolate).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -25,12 +28,13 @@
 static void usage(void) {
     fprintf(stderr,
             "usage: aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] "
-            "[--theta v0,v1,...] [--per-cu] [--levels]\n");
+            "[--theta v0,v1,...] [--per-cu] [--levels] [--err]\n");
 }
 
 int main(int argc, char **argv) {
     aq_problem p = {AQ_F_COSH4, 0, 0.0, 5.0, 1e-3, 0, 0}; /* aquadPartA.c:45-48 */
-    int nprocs = -1, gpus = 1, per_cu = 0, levels = 0;
+    int nprocs = -1, gpus = 1, per_cu = 0, levels = 0, with_err = 0;
+    aq_err err = {0.0, 0.0};
     double theta[AQ_MAX_PARAMS] = {0};
     int ntheta = 0;
     for (int i = 1; i < argc; ++i) {
@@ -61,11 +65,16 @@ int main(int argc, char **argv) {
             ++i;
         } else if (!strcmp(a, "--per-cu")) per_cu = 1;
         else if (!strcmp(a, "--levels")) levels = 1;
+        else if (!strcmp(a, "--err")) with_err = 1;
         else { usage(); return 2; }
     }
     if (p.integrand == AQ_F_PARAM ? (ntheta != aq_param_count() || gpus != 1) : ntheta != 0) {
         fprintf(stderr, "aquad: --f param takes --theta with %d value(s) (%s) on one GPU; no other integrand takes it\n",
                 aq_param_count(), aq_param_integrand_name());
+        return 2;
+    }
+    if (with_err && (gpus != 1 || levels)) {
+        fprintf(stderr, "aquad: --err runs on one GPU and keeps no level histograms\n");
         return 2;
     }
     if (nprocs == -1) nprocs = 1 + gpus;
@@ -90,7 +99,9 @@ int main(int argc, char **argv) {
     res.tasks_per_gpu = per_gpu;
     res.tasks_per_cu = cu;
     if (rc == AQ_OK) {
-        if (gpus == 1) {
+        if (with_err) {
+            rc = aq_integrate_err(ctx[0], &p, p.integrand == AQ_F_PARAM ? theta : NULL, &res, &err);
+        } else if (gpus == 1) {
             rc = p.integrand == AQ_F_PARAM ? aq_integrate_params(ctx[0], &p, theta, &res) : aq_integrate(ctx[0], &p, &res);
         } else {
             p.n_gpus = gpus;
@@ -114,6 +125,10 @@ int main(int argc, char **argv) {
             if (cu[c]) { tpp[1 + (k % cols)] += cu[c]; ++k; }
         aq_print_reference_procs(stdout, res.area, tpp, cols + 1);
         free(tpp);
+    }
+    if (with_err) {
+        fprintf(stdout, "Error estimate=%.6e\n", err.err_abs);
+        fprintf(stdout, "Extrapolated area=%.17g\n", aq_err_extrapolate(res.area, &err));
     }
     if (levels) {
         uint64_t t[AQ_MAX_LEVELS], l[AQ_MAX_LEVELS];
