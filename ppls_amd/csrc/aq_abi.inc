@@ -1,6 +1,9 @@
 // ================================================================================================
 // Host side: the C ABI of include/aquad.h (included by aquad.hip after the kernels).
 // ================================================================================================
+#include "aq_host_args.h"   // the argument rules and the chunk schedule (no HIP: tests/test_host_args.py)
+#include "aq_host_mem.h"    // owning device / pinned buffers, events, streams
+
 using namespace aq;
 
 namespace {
@@ -36,18 +39,8 @@ static_assert(XS_LIMBS == AQ_XS_LIMBS, "aquad.h and aq_xsum.h disagree on the ac
         }                                                                             \
     } while (0)
 
-int err_from_bits(unsigned bits) {
-    if (bits & ERRB_TIMEOUT) return AQ_ETIMEOUT;
-    if (bits & ERRB_OVERFLOW) return AQ_EOVERFLOW;
-    if (bits & ERRB_DEPTH) return AQ_EDEPTH;
-    return AQ_OK;
-}
-
-int floor_log2(unsigned long long v) {
-    int d = 0;
-    while ((2ull << d) <= v) ++d;
-    return d;
-}
+static_assert(HB_TIMEOUT == ERRB_TIMEOUT && HB_OVERFLOW == ERRB_OVERFLOW && HB_DEPTH == ERRB_DEPTH,
+              "aq_host_args.h and aq_device.h disagree on the error bits");
 
 bool integrand_ok(int f) { return f == AQ_F_COSH4 || f == AQ_F_SIN_RECIP || f == AQ_F_USER; }
 
@@ -96,124 +89,107 @@ struct aq_ctx {
     int grid = 0;                      // persistent workgroups per launch (one per CU, or AQ_GRID)
     std::unique_ptr<HostPool> pool;    // the batch front end's host threads (created on first use)
     int occ[4][2][6] = {};             // k_stream<FID,HIST> by Variant: resident workgroups per CU (0: not asked yet)
-    bool batch_heap = false;           // the batch front end's launches: the heap-seeding instance (HEAPS)
     bool coop = false;                 // AQ_COOP=1: cooperative launches
     bool histograms = true;
     double stall_ms = DEFAULT_STALL_MS;
+    // Every buffer, event and stream below frees itself (aq_host_mem.h); the streams come first, so they are
+    // destroyed last. DevBuf<T> x{&dev_bytes} counts in aq_ctx_device_bytes, DevBuf<T> x{} does not.
     unsigned long long dev_bytes = 0;  // device memory held
-    hipStream_t stream = nullptr;
-    ExpPair* d_tab = nullptr;
-    Ctl* d_ctl = nullptr;              // NSLOTS control blocks (totals, exact area, histograms)
-    QCtl* d_q = nullptr;               // two queue / termination blocks, used by launches in turn
+    Stream stream;
+    Stream s_h2d, s_d2h, s_pre;        // the batch front end's copy and pre-pass streams (created on first use)
+    DevBuf<ExpPair> d_tab{&dev_bytes};
+    DevBuf<Ctl> d_ctl{&dev_bytes};     // NSLOTS control blocks (totals, exact area, histograms)
+    DevBuf<QCtl> d_q{&dev_bytes};      // two queue / termination blocks, used by launches in turn
     int qsel = 0;                      // the block the next launch uses
-    unsigned long long* d_parts = nullptr;   // (NPARTS + 1) x grid per-workgroup pack_cu words (per-CU launches
-                                             // into slots < NPARTS, and the sync slot: parts_row)
-    double* d_parea = nullptr;               // ... and their area words (PCU_AREA: a double-double per workgroup)
-    bool sync_fold = false;                  // the next per-CU launch's reader folds its area words itself
-                                             // (k_fetch_sync, k_pack_group): no k_fold_parts after it
+    DevBuf<unsigned long long> d_parts{&dev_bytes};   // (NPARTS + 1) x grid per-workgroup pack_cu words (per-CU
+                                                      // launches into slots < NPARTS, and the sync slot: parts_row)
+    DevBuf<double> d_parea{&dev_bytes};               // ... and their area words (PCU_AREA: a double-double per workgroup)
     bool dirty[NSLOTS_ALL] = {};       // slot's sums / area used since they were last reset
     bool parts_dirty[NSLOTS_ALL] = {}; // slot's per-workgroup words written (per-CU launches)
     bool slot_hist[NSLOTS_ALL] = {};
-    double2* d_bounds = nullptr;       // NSLOTS {a, b}
-    int* d_shard = nullptr;            // NSLOTS per-integral shard (mixed launches)
-    double2* h_bounds = nullptr;       // pinned staging ring, NSTAGE x NSLOTS (a launch's copy may still be
+    DevBuf<double2> d_bounds{&dev_bytes};   // NSLOTS {a, b}
+    DevBuf<int> d_shard{&dev_bytes};   // NSLOTS per-integral shard (mixed launches)
+    PinBuf<double2> h_bounds;          // pinned staging ring, NSTAGE x NSLOTS (a launch's copy may still be
                                        // pending when the host queues the next launch)
-    int* h_shard = nullptr;            // pinned staging ring, NSTAGE x NSLOTS
-    hipEvent_t stage_ev[NSTAGE] = {};  // recorded after each staging copy
+    PinBuf<int> h_shard;               // pinned staging ring, NSTAGE x NSLOTS
+    Event stage_ev[NSTAGE];            // recorded after each staging copy
     int stage = 0;
-    Chunk* d_chunks = nullptr;
-    Cellar* d_cellar = nullptr;        // grid * NW per-wave HBM overflow stacks
-    unsigned* d_ready = nullptr;
+    DevBuf<Chunk> d_chunks{&dev_bytes};
+    DevBuf<Cellar> d_cellar{&dev_bytes};   // grid * NW per-wave HBM overflow stacks
+    DevBuf<unsigned> d_ready{&dev_bytes};
     unsigned epoch = 0;
-    LaunchHint* d_hint = nullptr;      // job-size hint carried from launch to launch
+    DevBuf<LaunchHint> d_hint{&dev_bytes};   // job-size hint carried from launch to launch
     HintState hint;                    // the workload the hint was measured on (aq_launch_plan.h)
     int gsplit_env = 0;                // AQ_GSPLIT: waves per job of a multi-integral launch (0 = default)
     // level path
-    DevResults* d_lres = nullptr;
-    Rec* d_front[2] = {nullptr, nullptr};
-    size_t front_cap = 0;              // records per buffer (0 unless both are allocated)
-    size_t front_bytes[2] = {0, 0};
-    unsigned* d_count = nullptr;
-    unsigned* h_fcount = nullptr;      // pinned: aq_frontier_integrate's per-level counts
-    double* d_facc = nullptr;          // aq_frontier_integrate's accumulator (8 doubles, device)
-    double* h_facc = nullptr;          // pinned copy
-    LevelPart* d_lparts = nullptr;     // frontier engine: per-block partials of one level step
+    DevBuf<DevResults> d_lres{&dev_bytes};
+    DevBuf<Rec> d_front[2] = {DevBuf<Rec>{&dev_bytes}, DevBuf<Rec>{&dev_bytes}};   // both of one size, or neither
+    DevBuf<unsigned> d_count{&dev_bytes};
+    PinBuf<unsigned> h_fcount;         // aq_frontier_integrate's per-level counts
+    DevBuf<double> d_facc{&dev_bytes}; // aq_frontier_integrate's accumulator (8 doubles, device)
+    PinBuf<double> h_facc;             // pinned copy
+    DevBuf<LevelPart> d_lparts{&dev_bytes};   // frontier engine: per-block partials of one level step
     bool defer_fold = false;           // aq_level_defer_fold: level steps leave their rows for one later fold
     int lp_pending = 0;                // level-step rows written and not yet folded
-    double* lp_acc = nullptr;          // ... into this accumulator
-    // batch front end: rows {area, tasks, accepted, error} and bounds, and the two copy streams that run
-    // beside the launches. The device keeps two chunks' bounds and two chunks' rows (rings indexed by
-    // chunk parity: at most chunk c + 1's bounds and chunks c, c - 1's rows are in flight) and one chunk's
-    // size-order buffers, bdev_rows integrals each (grow-only up to MAXK, whatever n: ADVICE r5 -- they
-    // had been sized to the whole batch, 72 B per integral); the pinned host copies cover the whole call
-    // (grow-only, bhost_cap integrals)
-    double* d_batch = nullptr;         // [2][bdev_rows][4]
-    double* h_batch = nullptr;         // [bhost_cap][4]
-    double2* d_bbounds = nullptr;      // [2][bdev_rows]
-    double2* h_bbounds = nullptr;      // [bhost_cap]
-    double2* d_bsorted = nullptr;      // the chunk's bounds in size order (k_batch_scatter; 2 parities)
-    unsigned* d_bkey = nullptr;        // size class per integral (k_batch_estimate)
-    unsigned* d_bperm = nullptr;       // sorted position -> integral (2 parities)
-    unsigned* d_bcnt = nullptr;        // EST_KEYS counts + EST_KEYS cursors
-    double* d_best = nullptr;          // the chunk's sum of size estimates (per chunk parity)
-    size_t bdev_rows = 0, bhost_cap = 0;
+    double* lp_acc = nullptr;          // ... into this accumulator (the caller's)
+    // batch front end: rows {area, tasks, accepted, error} and bounds. The device keeps two chunks' bounds
+    // and two chunks' rows (rings indexed by chunk parity: at most chunk c + 1's bounds and chunks c, c - 1's
+    // rows are in flight) and one chunk's size-order buffers, for the largest chunk so far (grow-only up to
+    // MAXK rows, whatever n: ADVICE r5 -- they had been sized to the whole batch, 72 B per integral); the
+    // pinned host copies cover the whole call (grow-only)
+    DevBuf<double> d_batch{&dev_bytes};      // [2][rows][4]
+    PinBuf<double> h_batch;                  // [n][4]
+    DevBuf<double2> d_bbounds{&dev_bytes};   // [2][rows]
+    PinBuf<double2> h_bbounds;               // [n]
+    DevBuf<double2> d_bsorted{&dev_bytes};   // the chunk's bounds in size order (k_batch_scatter; 2 parities)
+    DevBuf<unsigned> d_bkey{&dev_bytes};     // size class per integral (k_batch_estimate)
+    DevBuf<unsigned> d_bperm{&dev_bytes};    // sorted position -> integral (2 parities)
+    DevBuf<unsigned> d_bcnt{&dev_bytes};     // EST_KEYS counts + EST_KEYS cursors
+    DevBuf<double> d_best{&dev_bytes};       // the chunk's sum of size estimates (per chunk parity)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params; the
     // batch rings by the first aq_integrate_batch_params): NSLOTS + 1 rows on the device beside d_bounds,
     // their pinned staging ring, and the batch front end's rows -- two chunks' theta and two chunks' theta
     // in size order, sized like d_bbounds / d_bsorted, and the pinned copy of the whole call
-    double* d_theta = nullptr;         // [NSLOTS_ALL][nparams]
-    double* h_theta = nullptr;         // pinned staging ring, NSTAGE x NSLOTS x nparams
-    double* d_btheta = nullptr;        // [2][btheta_rows][nparams]
-    double* d_bthsorted = nullptr;     // [2][btheta_rows][nparams] (k_batch_scatter_theta)
-    double* h_btheta = nullptr;        // [btheta_hcap][nparams]
-    size_t btheta_rows = 0, btheta_hcap = 0;
+    DevBuf<double> d_theta{&dev_bytes};      // [NSLOTS_ALL][nparams]
+    PinBuf<double> h_theta;                  // pinned staging ring, NSTAGE x NSLOTS x nparams
+    DevBuf<double> d_btheta{&dev_bytes};     // [2][rows][nparams]
+    DevBuf<double> d_bthsorted{&dev_bytes};  // [2][rows][nparams] (k_batch_scatter_theta)
+    PinBuf<double> h_btheta;                 // [n][nparams]
     // error estimate (the ERR launches, aq_*_err), allocated by the first ERR call (ensure_err; the batch
     // rings by the first aq_integrate_batch_err): the slots' two sums, and the batch front end's rows -- two
     // chunks' {err_abs, err_signed} on the device and the pinned copy of the whole call
-    double* d_err = nullptr;           // [NSLOTS_ALL][2] = Σ|d|, Σd over the slot's accepted tasks
-    double* h_err = nullptr;           // pinned, one pair (aq_fetch_err)
+    DevBuf<double> d_err{&dev_bytes};  // [NSLOTS_ALL][2] = Σ|d|, Σd over the slot's accepted tasks
+    PinBuf<double> h_err;              // one pair (aq_fetch_err)
     bool err_dirty[NSLOTS_ALL] = {};   // slot's pair written since it was last zeroed
     bool slot_err[NSLOTS_ALL] = {};    // slot's last launch was an ERR launch (beside slot_hist)
     int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
-    double* d_berr = nullptr;          // [2][berr_rows][2]
-    double* h_berr = nullptr;          // [berr_hcap][2]
-    size_t berr_rows = 0, berr_hcap = 0;
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_pre = nullptr;
-    // eval buffers
-    double* d_x = nullptr;
-    double* d_y = nullptr;
-    size_t eval_cap = 0;
+    DevBuf<double> d_berr{&dev_bytes}; // [2][rows][2]
+    PinBuf<double> h_berr;             // [n][2]
+    // eval buffers (not counted)
+    DevBuf<double> d_x, d_y;
     // host staging
-    unsigned long long* h_parts = nullptr;  // pinned, grid words
-    SlotSums* h_sums = nullptr;        // pinned, one
-    XSum* h_area = nullptr;            // pinned, one
-    unsigned long long* h_hist = nullptr;  // pinned, 2 * AQ_MAX_LEVELS
-    DevResults* h_lres = nullptr;      // pinned
-    SyncOut* h_sync = nullptr;         // pinned, coherent: k_fetch_sync's target (the synchronous path)
+    PinBuf<unsigned long long> h_parts;   // grid words
+    PinBuf<SlotSums> h_sums;           // one
+    PinBuf<XSum> h_area;               // one
+    PinBuf<unsigned long long> h_hist; // 2 * AQ_MAX_LEVELS
+    PinBuf<DevResults> h_lres;
+    PinBuf<SyncOut> h_sync;            // coherent: k_fetch_sync's target (the synchronous path)
     SyncOut* d_sync = nullptr;         // its device address
     unsigned long long sync_seq = 0;   // the last synchronous call's sequence number (SyncOut::seq)
     HostOut last;
     bool last_valid = false;
     // diagnostics
-    unsigned long long* d_diag = nullptr;
-    unsigned long long* d_cu_acc = nullptr;   // [AQ_CU_SLOTS] tasks per CU slot since the last reset (every launch)
+    DevBuf<unsigned long long> d_diag;                // (not counted)
+    DevBuf<unsigned long long> d_cu_acc{&dev_bytes};  // [AQ_CU_SLOTS] tasks per CU slot since the last reset (every launch)
     // timing
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+    std::vector<std::pair<Event, Event>> ev_pending;
+    std::vector<std::pair<Event, Event>> ev_free;
     double timed_ms = 0.0;
     unsigned long long timed_launches = 0;
 };
 
 namespace {
-
-template <typename T>
-int dmalloc(aq_ctx* c, T** p, size_t bytes, bool zero) {
-    AQ_HIP(hipMalloc(reinterpret_cast<void**>(p), bytes));
-    c->dev_bytes += bytes;
-    if (zero) AQ_HIP(hipMemset(*p, 0, bytes));
-    return AQ_OK;
-}
 
 // Return slots [s, s+k) to the all-zero state if any was used since it was last reset (k_reset:
 // sums, exact area, queue words; histograms when written). Per-workgroup words (per-CU launches only)
@@ -281,46 +257,65 @@ const void* stream_kernel_err(Variant v) {
 
 // Kernel timing (aq_kernel_timing / aq_kernel_time): a launch's event pair, reused from the free list, its
 // first event recorded ahead of the launch and its second after it; aq_kernel_time reads the pending pairs.
-using EventPair = std::pair<hipEvent_t, hipEvent_t>;
+using EventPair = std::pair<Event, Event>;
 int timing_begin(aq_ctx* ctx, EventPair& ev) {
     if (!ctx->timing) return AQ_OK;
     if (!ctx->ev_free.empty()) {
-        ev = ctx->ev_free.back();
+        ev = std::move(ctx->ev_free.back());
         ctx->ev_free.pop_back();
     } else {
-        AQ_HIP(hipEventCreate(&ev.first));
-        AQ_HIP(hipEventCreate(&ev.second));
+        AQ_HIP(ev.first.create());
+        AQ_HIP(ev.second.create());
     }
     AQ_HIP(hipEventRecord(ev.first, ctx->stream));
     return AQ_OK;
 }
-int timing_end(aq_ctx* ctx, const EventPair& ev) {
+int timing_end(aq_ctx* ctx, EventPair& ev) {
     if (!ctx->timing) return AQ_OK;
     AQ_HIP(hipEventRecord(ev.second, ctx->stream));
-    ctx->ev_pending.push_back(ev);
+    ctx->ev_pending.push_back(std::move(ev));
     return AQ_OK;
 }
 
-// One persistent launch of k integrals (slots first_slot ..). shard_of: per-integral shard of
-// nshards (nullptr: every integral is shard `shard`). dev_bounds: the k {a, b} already on the device
-// (the batch front end copies them ahead on its own stream), else they are staged and copied here.
+// One persistent launch: k integrals of one integrand into slots first_slot ...
+struct LaunchArgs {
+    int integrand = AQ_F_COSH4;          // AQ_F_*
+    int k = 0;
+    const double* a = nullptr;           // the k bounds on the host
+    const double* b = nullptr;
+    const int32_t* shard_of = nullptr;   // per-integral shard of nshards (nullptr: every integral is shard `shard`)
+    double eps = 0.0;
+    int max_depth = 0, shard = 0, nshards = 1, first_slot = 0;
+    const double2* dev_bounds = nullptr; // the k {a, b} already on the device (the batch front end copies them ahead
+                                         // on its own stream), else they are staged and copied by the launch
+    const double* theta = nullptr;       // AQ_F_PARAM: the k parameter rows on the host (staged and copied by the
+                                         // launch, per-CU launches too: theta is not a kernel argument), or
+    const double* dev_theta = nullptr;   // ... already on the device in the launch's order (the batch front end)
+    bool err = false;                    // an ERR launch (its instances keep no histograms, whatever `hist`)
+    bool hist = false;                   // per-level histograms (the callers pass ctx->histograms; the batch none)
+    bool heap = false;                   // the batch front end's launches: the heap-seeding instance (HEAPS)
+    bool sync_fold = false;              // a per-CU launch's reader folds its area words itself (k_fetch_sync,
+                                         // k_pack_group): no k_fold_parts after it
+};
+
 // The launch's shape -- instance, waves, shares, seed depth, tail, job mode -- is plan_launch's
 // (aq_launch_plan.h); this enqueues it.
 template <int FID, bool HIST>
-int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const int32_t* shard_of, double eps,
-                  int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
-                  const double* theta = nullptr, const double* dev_theta = nullptr, bool err = false) {
+int launch_stream(aq_ctx* ctx, const LaunchArgs& g) {
     static_assert(FID >= 0 && FID < 4, "aq_ctx::occ holds one row per integrand");
-    // err: an ERR launch (its instances keep no histograms: the callers pass HIST = false); ctx->d_err exists
+    const int k = g.k, max_depth = g.max_depth, shard = g.shard, nshards = g.nshards, first_slot = g.first_slot;
+    const double eps = g.eps, *a = g.a, *b = g.b, *theta = g.theta, *dev_theta = g.dev_theta;
+    const int32_t* shard_of = g.shard_of;
+    const double2* dev_bounds = g.dev_bounds;
+    const bool err = g.err;
+    // an ERR launch's instances keep no histograms (launch passes HIST = false); ctx->d_err exists
     if (err && (HIST || !ctx->d_err)) return AQ_EINVAL;
-    // F_PARAM: the k parameter rows, on the host (staged and copied here, per-CU launches too: theta is
-    // not a kernel argument) or already on the device in the launch's order (the batch front end)
     constexpr int NP = param::nparams;
     const bool stage_theta = FID == F_PARAM && !dev_theta;
     if (FID == F_PARAM && !theta && !dev_theta) return AQ_EINVAL;
     const int G = ctx->grid;
     const LaunchRequest rq{FID, G, k, shard_of != nullptr, nshards, first_slot, ctx->d_diag != nullptr,
-                           ctx->batch_heap, ctx->gsplit_env, eps, err};
+                           g.heap, ctx->gsplit_env, eps, err};
     const LaunchPlan plan = plan_launch(rq, ctx->hint);
     if (plan.rc) return plan.rc;   // refused before anything is enqueued
     // per-CU launches pass their bounds as kernel arguments: no staging copy
@@ -400,7 +395,7 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     P.adaptive = plan.adaptive;
     if (FID == F_PARAM) P.theta = dev_theta ? dev_theta : ctx->d_theta + (size_t)first_slot * NP;
     ctx->hint = plan.hint;   // (committed before the launch: a failing launch leaves the new state)
-    EventPair ev{nullptr, nullptr};
+    EventPair ev;
     if ((rc = timing_begin(ctx, ev))) return rc;
     void* args[] = {&P};
     if (ctx->coop)
@@ -411,7 +406,7 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     if ((rc = timing_end(ctx, ev))) return rc;
     // a per-CU launch leaves its area in per-workgroup words (PCU_AREA): folded into the slots here, for
     // every reader, unless the synchronous path's own read-back folds them (k_fetch_sync, k_pack_group)
-    if (pcu && !ctx->sync_fold) {
+    if (pcu && !g.sync_fold) {
         hipLaunchKernelGGL(k_fold_parts, dim3(k), dim3(256), 0, ctx->stream, ctx->d_ctl, (const double*)P.parea,
                            ctx->grid, first_slot);
         AQ_HIP(hipGetLastError());
@@ -424,27 +419,14 @@ int launch_stream(aq_ctx* ctx, int k, const double* a, const double* b, const in
     return AQ_OK;
 }
 
-int launch_any(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const int32_t* shard_of,
-               double eps, int max_depth, int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
-               bool err = false) {
-    return with_fid(integrand, [&](auto F) {
-        constexpr int FID = decltype(F)::value;
-        if (err)
-            return launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds,
-                                             nullptr, nullptr, true);
-        return ctx->histograms
-            ? launch_stream<FID, true>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds)
-            : launch_stream<FID, false>(ctx, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot, dev_bounds);
-    });
-}
-
 // The parametrised family's buffers, on the first parametrised call (a fresh context holds none of them:
 // aq_ctx_device_bytes does not move until then).
 int ensure_params(aq_ctx* ctx) {
     if (ctx->d_theta) return AQ_OK;
     constexpr size_t NP = (size_t)param::nparams;
-    if (!ctx->h_theta) AQ_HIP(hipHostMalloc(&ctx->h_theta, sizeof(double) * NP * NSLOTS * NSTAGE, hipHostMallocDefault));
-    return dmalloc(ctx, &ctx->d_theta, sizeof(double) * NP * NSLOTS_ALL, false);
+    AQ_HIP(ctx->h_theta.grow(NP * NSLOTS * NSTAGE));
+    AQ_HIP(ctx->d_theta.alloc(NP * NSLOTS_ALL, false));
+    return AQ_OK;
 }
 
 // The error estimate's slot sums, on the first ERR call (a fresh context and the plain calls hold none of
@@ -452,25 +434,28 @@ int ensure_params(aq_ctx* ctx) {
 // slots zero between launches.
 int ensure_err(aq_ctx* ctx) {
     if (ctx->d_err) return AQ_OK;
-    if (!ctx->h_err) AQ_HIP(hipHostMalloc(&ctx->h_err, 2 * sizeof(double), hipHostMallocDefault));
-    return dmalloc(ctx, &ctx->d_err, 2 * sizeof(double) * NSLOTS_ALL, true);
+    AQ_HIP(ctx->h_err.grow(2));
+    AQ_HIP(ctx->d_err.alloc(2 * (size_t)NSLOTS_ALL, true));
+    return AQ_OK;
 }
 
-// launch_any for AQ_F_PARAM (with_fid stays the three fixed integrands': no level or frontier kernel
-// is instantiated for id 3)
-int launch_params(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta, double eps, int max_depth,
-                  int shard, int nshards, int first_slot, const double2* dev_bounds = nullptr,
-                  const double* dev_theta = nullptr, bool err = false) {
-    const int rc = ensure_params(ctx);
-    if (rc) return rc;
-    if (err)
-        return launch_stream<F_PARAM, false>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
-                                             theta, dev_theta, true);
-    return ctx->histograms
-        ? launch_stream<F_PARAM, true>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
-                                       theta, dev_theta)
-        : launch_stream<F_PARAM, false>(ctx, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, dev_bounds,
-                                        theta, dev_theta);
+// with_fid for the stream launches: AQ_F_PARAM too (with_fid stays the three fixed integrands': no level or
+// frontier kernel is instantiated for id 3)
+template <typename Fn>
+auto with_stream_fid(int integrand, Fn&& f) {
+    if (integrand == AQ_F_PARAM) return f(std::integral_constant<int, F_PARAM>{});
+    return with_fid(integrand, f);
+}
+
+// Enqueue one launch, with the buffers its family needs.
+int launch(aq_ctx* ctx, const LaunchArgs& g) {
+    int rc;
+    if (g.err && (rc = ensure_err(ctx))) return rc;
+    if (g.integrand == AQ_F_PARAM && (rc = ensure_params(ctx))) return rc;
+    return with_stream_fid(g.integrand, [&](auto F) {
+        constexpr int FID = decltype(F)::value;
+        return g.hist && !g.err ? launch_stream<FID, true>(ctx, g) : launch_stream<FID, false>(ctx, g);
+    });
 }
 
 // One integral of the parametrised family: the engine's bounds rule, finite parameters, the plug-in's domain.
@@ -531,18 +516,44 @@ static int finish_fetch(aq_ctx* ctx, SlotSums sm, const XSum& area, const unsign
     return err_from_bits(h.error);
 }
 
-int fetch_slot(aq_ctx* ctx, int slot, aq_result* out) {
+// Copy a slot's words into the pinned staging and wait for them: its sums and exact area, its per-workgroup
+// words if a per-CU launch wrote them, its histograms if asked for and kept. *sm: the sums, their `pcu` flag
+// cleared unless the per-workgroup words came along.
+int read_slot(aq_ctx* ctx, int slot, bool hist, SlotSums* sm) {
     if (ctx->parts_dirty[slot])
         AQ_HIP(hipMemcpyAsync(ctx->h_parts, ctx->d_parts + 2 * parts_row(slot) * ctx->grid,
                               2 * sizeof(unsigned long long) * (size_t)ctx->grid, hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipMemcpyAsync(ctx->h_sums, &ctx->d_ctl[slot].sums, sizeof(SlotSums), hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipMemcpyAsync(ctx->h_area, &ctx->d_ctl[slot].area, sizeof(XSum), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->slot_hist[slot])
+    if (hist && ctx->slot_hist[slot])
         AQ_HIP(hipMemcpyAsync(ctx->h_hist, ctx->d_ctl[slot].hist, sizeof(unsigned long long) * 2 * AQ_MAX_LEVELS,
                               hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipStreamSynchronize(ctx->stream));
-    return finish_fetch(ctx, *ctx->h_sums, *ctx->h_area, ctx->parts_dirty[slot] ? ctx->h_parts : nullptr,
-                        ctx->slot_hist[slot] ? ctx->h_hist : nullptr, out);
+    *sm = *ctx->h_sums;
+    if (!ctx->parts_dirty[slot]) sm->pcu = 0;
+    return AQ_OK;
+}
+
+int fetch_slot(aq_ctx* ctx, int slot, aq_result* out) {
+    SlotSums sm;
+    const int rc = read_slot(ctx, slot, true, &sm);
+    if (rc) return rc;
+    return finish_fetch(ctx, sm, *ctx->h_area, ctx->parts_dirty[slot] ? ctx->h_parts.get() : nullptr,
+                        ctx->slot_hist[slot] ? ctx->h_hist.get() : nullptr, out);
+}
+
+// a slot's exact row (aq_fetch_exact): limbs, tasks, accepted, spilled, levels | error bits << 32
+int fetch_exact_slot(aq_ctx* ctx, int slot, int64_t* row) {
+    SlotSums s;
+    const int rc = read_slot(ctx, slot, false, &s);
+    if (rc) return rc;
+    for (int i = 0; i < XS_LIMBS; ++i) row[i] = ctx->h_area->limb[i];
+    const Counts k = slot_counts(s, ctx->h_parts, ctx->grid);
+    row[XS_LIMBS] = (int64_t)k.tasks;
+    row[XS_LIMBS + 1] = (int64_t)k.leaves;
+    row[XS_LIMBS + 2] = (int64_t)s.spilled;
+    row[XS_LIMBS + 3] = (int64_t)k.levels | ((int64_t)s.error << 32);
+    return err_from_bits(s.error);
 }
 
 // Wait for k_fetch_sync's sequence number in pinned host memory: a spin on one coherent word, with a
@@ -561,7 +572,9 @@ static bool wait_sync_seq(aq_ctx* ctx, unsigned long long want) {
                 return __atomic_load_n(&ctx->h_sync->seq, __ATOMIC_ACQUIRE) == want;
             }
         }
+#if defined(__x86_64__) || defined(__i386__)
         __builtin_ia32_pause();
+#endif
     }
 }
 
@@ -599,23 +612,23 @@ static int fetch_sync(aq_ctx* ctx, aq_result* out, aq_err* err = nullptr) {
     return finish_fetch(ctx, o.sums, o.area, wp ? o.parts : nullptr, wh ? o.hist : nullptr, out);
 }
 
-bool slot_range_ok(int first, int n) { return first >= 0 && n >= 0 && n <= NSLOTS && first < NSLOTS; }
-
 }  // namespace
 
-// The RCCL group (aq_integrate_group).
+// The RCCL group (aq_integrate_group). The vectors hold one entry per member driven by this process.
 struct aq_group {
     int nranks = 0;
     int grid = 0;
-    bool own_ctx_order = false;
-    std::vector<aq_ctx*> ctx;             // members driven by this process
+    std::vector<aq_ctx*> ctx;
     std::vector<int> rank;                // their ranks
-    std::vector<ncclComm_t> comm;
-    std::vector<long long*> d_sum;        // per member: GROUP_SUM int64 (all-reduced in place)
-    std::vector<unsigned long long*> d_mine;   // per member: 3 + grid words (this rank's contribution)
-    std::vector<unsigned long long*> d_all;    // per member: nranks * (3 + grid) words (all-gathered)
-    long long* h_sum = nullptr;           // pinned copies of member 0's results
-    unsigned long long* h_all = nullptr;
+    std::vector<ncclComm_t> comm;         // (null until the communicator exists)
+    std::vector<DevBuf<long long>> d_sum;            // GROUP_SUM int64 (all-reduced in place)
+    std::vector<DevBuf<unsigned long long>> d_mine;  // 3 + grid words (this rank's contribution)
+    std::vector<DevBuf<unsigned long long>> d_all;   // nranks * (3 + grid) words (all-gathered)
+    PinBuf<long long> h_sum;              // pinned copies of member 0's results
+    PinBuf<unsigned long long> h_all;
+
+    aq_group(int nranks_, int members) : nranks(nranks_), comm(members, nullptr), d_sum(members), d_mine(members),
+                                         d_all(members) {}
 };
 
 namespace {
@@ -624,17 +637,31 @@ int group_alloc(aq_group* g) {
     const size_t info = 3 + (size_t)g->grid;
     for (size_t m = 0; m < g->ctx.size(); ++m) {
         AQ_HIP(hipSetDevice(g->ctx[m]->device));
-        long long* s = nullptr;
-        unsigned long long *mine = nullptr, *all = nullptr;
-        AQ_HIP(hipMalloc(&s, sizeof(long long) * GROUP_SUM));
-        AQ_HIP(hipMalloc(&mine, sizeof(unsigned long long) * info));
-        AQ_HIP(hipMalloc(&all, sizeof(unsigned long long) * info * g->nranks));
-        g->d_sum.push_back(s);
-        g->d_mine.push_back(mine);
-        g->d_all.push_back(all);
+        AQ_HIP(g->d_sum[m].alloc(GROUP_SUM, false));
+        AQ_HIP(g->d_mine[m].alloc(info, false));
+        AQ_HIP(g->d_all[m].alloc(info * g->nranks, false));
     }
-    AQ_HIP(hipHostMalloc(&g->h_sum, sizeof(long long) * GROUP_SUM, hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&g->h_all, sizeof(unsigned long long) * info * g->nranks, hipHostMallocDefault));
+    AQ_HIP(g->h_sum.alloc(GROUP_SUM, false));
+    AQ_HIP(g->h_all.alloc(info * g->nranks, false));
+    return AQ_OK;
+}
+
+// The end of aq_group_create / aq_group_join, after the communicator's `init` call returned r: the group's
+// buffers, and the group published -- or destroyed.
+int group_finish(aq_group* g, ncclResult_t r, const char* init, aq_group** out) {
+    int rc = AQ_OK;
+    if (r != ncclSuccess) {
+        fprintf(stderr, "aquad: %s: %s\n", init, ncclGetErrorString(r));
+        g->comm.assign(g->comm.size(), nullptr);
+        rc = AQ_ERCCL;
+    } else {
+        rc = group_alloc(g);
+    }
+    if (rc) {
+        aq_group_destroy(g);
+        return rc;
+    }
+    *out = g;
     return AQ_OK;
 }
 
@@ -709,37 +736,36 @@ static int ctx_init(aq_ctx* c, int device) {
         const double v = atof(e);
         if (v > 0) c->stall_ms = v;
     }
-    AQ_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    int rc;
-    if ((rc = dmalloc(c, &c->d_tab, sizeof(ExpPair) * 128, false))) return rc;
+    AQ_HIP(c->stream.create());
+    const size_t G = (size_t)c->grid;
+    AQ_HIP(c->d_tab.alloc(128, false));
     AQ_HIP(hipMemcpy(c->d_tab, aq_exp_tab_host, sizeof(ExpPair) * 128, hipMemcpyHostToDevice));
-    if ((rc = dmalloc(c, &c->d_ctl, sizeof(Ctl) * NSLOTS_ALL, true))) return rc;
-    if ((rc = dmalloc(c, &c->d_parts, 2 * sizeof(unsigned long long) * (size_t)(NPARTS + 1) * c->grid, true))) return rc;
-    if ((rc = dmalloc(c, &c->d_parea, 2 * sizeof(double) * (size_t)(NPARTS + 1) * c->grid, true))) return rc;
-    if ((rc = dmalloc(c, &c->d_bounds, sizeof(double2) * NSLOTS_ALL, false))) return rc;
-    if ((rc = dmalloc(c, &c->d_shard, sizeof(int) * NSLOTS_ALL, false))) return rc;
-    if ((rc = dmalloc(c, &c->d_hint, sizeof(LaunchHint), true))) return rc;
-    if ((rc = dmalloc(c, &c->d_q, 2 * sizeof(QCtl), true))) return rc;
-    if ((rc = dmalloc(c, &c->d_cu_acc, sizeof(unsigned long long) * AQ_CU_SLOTS, true))) return rc;
-    AQ_HIP(hipHostMalloc(&c->h_bounds, sizeof(double2) * NSLOTS * NSTAGE, hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_shard, sizeof(int) * NSLOTS * NSTAGE, hipHostMallocDefault));
-    for (int i = 0; i < NSTAGE; ++i) {
-        AQ_HIP(hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming));
-        AQ_HIP(hipEventRecord(c->stage_ev[i], c->stream));
+    AQ_HIP(c->d_ctl.alloc(NSLOTS_ALL, true));
+    AQ_HIP(c->d_parts.alloc(2 * (size_t)(NPARTS + 1) * G, true));
+    AQ_HIP(c->d_parea.alloc(2 * (size_t)(NPARTS + 1) * G, true));
+    AQ_HIP(c->d_bounds.alloc(NSLOTS_ALL, false));
+    AQ_HIP(c->d_shard.alloc(NSLOTS_ALL, false));
+    AQ_HIP(c->d_hint.alloc(1, true));
+    AQ_HIP(c->d_q.alloc(2, true));
+    AQ_HIP(c->d_cu_acc.alloc(AQ_CU_SLOTS, true));
+    AQ_HIP(c->h_bounds.alloc((size_t)NSLOTS * NSTAGE, false));
+    AQ_HIP(c->h_shard.alloc((size_t)NSLOTS * NSTAGE, false));
+    for (Event& e : c->stage_ev) {
+        AQ_HIP(e.create(hipEventDisableTiming));
+        AQ_HIP(hipEventRecord(e, c->stream));
     }
-    if ((rc = dmalloc(c, &c->d_chunks, sizeof(Chunk) * (size_t)QCAP, false))) return rc;
-    if ((rc = dmalloc(c, &c->d_cellar, sizeof(Cellar) * (size_t)c->grid * NW, false))) return rc;
-    if ((rc = dmalloc(c, &c->d_ready, sizeof(unsigned) * (size_t)QCAP * READY_STRIDE, true))) return rc;
-    AQ_HIP(hipHostMalloc(&c->h_parts, 2 * sizeof(unsigned long long) * (size_t)c->grid, hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_sums, sizeof(SlotSums), hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_area, sizeof(XSum), hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_hist, sizeof(unsigned long long) * 2 * AQ_MAX_LEVELS, hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_lres, sizeof(DevResults), hipHostMallocDefault));
-    AQ_HIP(hipHostMalloc(&c->h_sync, sizeof(SyncOut), hipHostMallocCoherent | hipHostMallocMapped));
+    AQ_HIP(c->d_chunks.alloc(QCAP, false));
+    AQ_HIP(c->d_cellar.alloc(G * NW, false));
+    AQ_HIP(c->d_ready.alloc((size_t)QCAP * READY_STRIDE, true));
+    AQ_HIP(c->h_parts.alloc(2 * G, false));
+    AQ_HIP(c->h_sums.alloc(1, false));
+    AQ_HIP(c->h_area.alloc(1, false));
+    AQ_HIP(c->h_hist.alloc(2 * AQ_MAX_LEVELS, false));
+    AQ_HIP(c->h_lres.alloc(1, false));
+    AQ_HIP(c->h_sync.alloc(1, true, hipHostMallocCoherent | hipHostMallocMapped));
     AQ_HIP(hipHostGetDevicePointer((void**)&c->d_sync, c->h_sync, 0));
-    memset(c->h_sync, 0, sizeof(SyncOut));
-    if ((rc = dmalloc(c, &c->d_lres, sizeof(DevResults), false))) return rc;
-    if ((rc = dmalloc(c, &c->d_count, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), false))) return rc;
+    AQ_HIP(c->d_lres.alloc(1, false));
+    AQ_HIP(c->d_count.alloc(AQ_MAX_LEVELS + 2, false));
     AQ_HIP(hipDeviceSynchronize());
     return AQ_OK;
 }
@@ -764,65 +790,9 @@ void aq_ctx_destroy(aq_ctx* c) {
     if (!c) return;
     c->pool.reset();
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev_pending) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto& e : c->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    (void)hipFree(c->d_tab);
-    (void)hipFree(c->d_ctl);
-    (void)hipFree(c->d_parts);
-    (void)hipFree(c->d_parea);
-    (void)hipFree(c->d_bounds);
-    (void)hipFree(c->d_shard);
-    (void)hipFree(c->d_hint);
-    (void)hipFree(c->d_q);
-    (void)hipFree(c->d_chunks);
-    (void)hipFree(c->d_cellar);
-    (void)hipFree(c->d_ready);
-    (void)hipFree(c->d_lres);
-    (void)hipFree(c->d_diag);
-    (void)hipFree(c->d_cu_acc);
-    (void)hipFree(c->d_front[0]);
-    (void)hipFree(c->d_front[1]);
-    (void)hipFree(c->d_count);
-    (void)hipFree(c->d_facc);
-    if (c->h_fcount) (void)hipHostFree(c->h_fcount);
-    if (c->h_facc) (void)hipHostFree(c->h_facc);
-    (void)hipFree(c->d_x);
-    (void)hipFree(c->d_batch);
-    (void)hipFree(c->d_lparts);
-    (void)hipFree(c->d_y);
-    if (c->h_batch) (void)hipHostFree(c->h_batch);
-    (void)hipFree(c->d_bbounds);
-    if (c->h_bbounds) (void)hipHostFree(c->h_bbounds);
-    (void)hipFree(c->d_bsorted);
-    (void)hipFree(c->d_bkey);
-    (void)hipFree(c->d_bperm);
-    (void)hipFree(c->d_bcnt);
-    (void)hipFree(c->d_best);
-    (void)hipFree(c->d_theta);
-    (void)hipFree(c->d_err);
-    (void)hipFree(c->d_berr);
-    if (c->h_err) (void)hipHostFree(c->h_err);
-    if (c->h_berr) (void)hipHostFree(c->h_berr);
-    (void)hipFree(c->d_btheta);
-    (void)hipFree(c->d_bthsorted);
-    if (c->h_theta) (void)hipHostFree(c->h_theta);
-    if (c->h_btheta) (void)hipHostFree(c->h_btheta);
-    if (c->s_h2d) { (void)hipStreamSynchronize(c->s_h2d); (void)hipStreamDestroy(c->s_h2d); }
-    if (c->s_pre) { (void)hipStreamSynchronize(c->s_pre); (void)hipStreamDestroy(c->s_pre); }
-    if (c->s_d2h) { (void)hipStreamSynchronize(c->s_d2h); (void)hipStreamDestroy(c->s_d2h); }
-    if (c->h_bounds) (void)hipHostFree(c->h_bounds);
-    if (c->h_shard) (void)hipHostFree(c->h_shard);
-    for (int i = 0; i < NSTAGE; ++i)
-        if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
-    if (c->h_parts) (void)hipHostFree(c->h_parts);
-    if (c->h_sums) (void)hipHostFree(c->h_sums);
-    if (c->h_area) (void)hipHostFree(c->h_area);
-    if (c->h_hist) (void)hipHostFree(c->h_hist);
-    if (c->h_lres) (void)hipHostFree(c->h_lres);
-    if (c->h_sync) (void)hipHostFree(c->h_sync);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    for (const Stream* s : {&c->stream, &c->s_h2d, &c->s_pre, &c->s_d2h})
+        if (*s) (void)hipStreamSynchronize(*s);
+    delete c;   // (the members free themselves: aq_host_mem.h)
 }
 
 int aq_ctx_num_cus(const aq_ctx* c) { return c ? c->num_cus : 0; }
@@ -850,13 +820,8 @@ int aq_set_diagnostics(aq_ctx* c, int enable) {
     if (!c) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(c->device));
     AQ_HIP(hipStreamSynchronize(c->stream));
-    if (enable && !c->d_diag) {
-        AQ_HIP(hipMalloc(&c->d_diag, sizeof(unsigned long long) * DIAG_WORDS * MAXG));
-        AQ_HIP(hipMemset(c->d_diag, 0, sizeof(unsigned long long) * DIAG_WORDS * MAXG));
-    } else if (!enable && c->d_diag) {
-        (void)hipFree(c->d_diag);
-        c->d_diag = nullptr;
-    }
+    if (enable && !c->d_diag) AQ_HIP(c->d_diag.alloc((size_t)DIAG_WORDS * MAXG, true));
+    if (!enable) c->d_diag.reset();
     return AQ_OK;
 }
 
@@ -873,25 +838,54 @@ int aq_async_slots(void) { return NSLOTS; }
 
 int aq_max_integrals_per_launch(void) { return MAXK; }
 
-static int many_common(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const int32_t* shard_of,
-                       double eps, int max_depth, int shard, int nshards, int first_slot, int slot_limit = NSLOTS) {
-    if (!ctx || k < 1 || k > MAXK || !a || !b) return AQ_EINVAL;
-    if (!integrand_ok(integrand)) return AQ_EINVAL;
-    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
-    if (nshards < 1 || nshards > 64) return AQ_EINVAL;
-    if (!shard_of && (shard < 0 || shard >= nshards)) return AQ_EINVAL;
-    if (first_slot < 0 || first_slot + k > slot_limit) return AQ_EINVAL;
-    for (int i = 0; i < k; ++i) {
-        if (!bounds_ok(integrand, a[i], b[i])) return AQ_EINVAL;
-        if (shard_of && (shard_of[i] < 0 || shard_of[i] >= nshards)) return AQ_EINVAL;
+// theta goes with AQ_F_PARAM and with nothing else
+static bool theta_ok(int integrand, const double* theta) {
+    return integrand == AQ_F_PARAM ? theta != nullptr : (integrand_ok(integrand) && theta == nullptr);
+}
+
+// Every launch entry point's end: the argument rules (the ranges of aq_host_args.h, each integral's domain and
+// shard), then the launch with the context's histogram setting. The synchronous calls pass NSLOTS_ALL as the
+// slot limit (SYNC_SLOT).
+static int checked_launch(aq_ctx* ctx, LaunchArgs g, int slot_limit = NSLOTS) {
+    if (!ctx || !g.a || !g.b || !theta_ok(g.integrand, g.theta)) return AQ_EINVAL;
+    if (!launch_ranges_ok(g.k, g.eps, g.max_depth, g.shard, g.nshards, g.shard_of != nullptr, g.first_slot, slot_limit))
+        return AQ_EINVAL;
+    for (int i = 0; i < g.k; ++i) {
+        if (g.theta ? !params_ok(g.a[i], g.b[i], g.theta + (size_t)i * param::nparams)
+                    : !bounds_ok(g.integrand, g.a[i], g.b[i]))
+            return AQ_EINVAL;
+        if (g.shard_of && (g.shard_of[i] < 0 || g.shard_of[i] >= g.nshards)) return AQ_EINVAL;
     }
     AQ_HIP(hipSetDevice(ctx->device));
-    return launch_any(ctx, integrand, k, a, b, shard_of, eps, max_depth, shard, nshards, first_slot);
+    g.hist = ctx->histograms;
+    return launch(ctx, g);
+}
+
+// the arguments of k integrals as one shard
+static LaunchArgs many_args(int integrand, int k, const double* a, const double* b, const double* theta, double eps,
+                            int max_depth, int shard, int nshards, int first_slot) {
+    LaunchArgs g;
+    g.integrand = integrand;
+    g.k = k;
+    g.a = a;
+    g.b = b;
+    g.theta = theta;
+    g.eps = eps;
+    g.max_depth = max_depth;
+    g.shard = shard;
+    g.nshards = nshards;
+    g.first_slot = first_slot;
+    return g;
+}
+
+// ... and of a synchronous call's one integral, into SYNC_SLOT
+static LaunchArgs sync_args(const aq_problem* p, const double* theta, int shard, int nshards) {
+    return many_args(p->integrand, 1, &p->a, &p->b, theta, p->eps, p->max_depth, shard, nshards, SYNC_SLOT);
 }
 
 int aq_integrate_many_async(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, double eps,
                             int max_depth, int shard, int nshards, int first_slot) {
-    return many_common(ctx, integrand, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot);
+    return checked_launch(ctx, many_args(integrand, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot));
 }
 
 int aq_integrate_mixed_async(aq_ctx* ctx, int integrand, int k, const double* a, const double* b,
@@ -904,7 +898,9 @@ int aq_integrate_mixed_async(aq_ctx* ctx, int integrand, int k, const double* a,
             if (shard[i] != 0) return AQ_EINVAL;
         shard = nullptr;
     }
-    return many_common(ctx, integrand, k, a, b, shard, eps, max_depth, 0, nshards, first_slot);
+    LaunchArgs g = many_args(integrand, k, a, b, nullptr, eps, max_depth, 0, nshards, first_slot);
+    g.shard_of = shard;
+    return checked_launch(ctx, g);
 }
 
 int aq_integrate_async(aq_ctx* ctx, const aq_problem* p, int shard, int nshards, int slot) {
@@ -940,24 +936,6 @@ int aq_fetch(aq_ctx* ctx, int slot, aq_result* res) {
     return fetch_slot(ctx, slot, res);
 }
 
-static int fetch_exact_slot(aq_ctx* ctx, int slot, int64_t* row) {
-    if (ctx->parts_dirty[slot])
-        AQ_HIP(hipMemcpyAsync(ctx->h_parts, ctx->d_parts + 2 * parts_row(slot) * ctx->grid,
-                              2 * sizeof(unsigned long long) * (size_t)ctx->grid, hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_sums, &ctx->d_ctl[slot].sums, sizeof(SlotSums), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_area, &ctx->d_ctl[slot].area, sizeof(XSum), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < XS_LIMBS; ++i) row[i] = ctx->h_area->limb[i];
-    SlotSums s = *ctx->h_sums;
-    if (!ctx->parts_dirty[slot]) s.pcu = 0;
-    const Counts k = slot_counts(s, ctx->h_parts, ctx->grid);
-    row[XS_LIMBS] = (int64_t)k.tasks;
-    row[XS_LIMBS + 1] = (int64_t)k.leaves;
-    row[XS_LIMBS + 2] = (int64_t)s.spilled;
-    row[XS_LIMBS + 3] = (int64_t)k.levels | ((int64_t)s.error << 32);
-    return err_from_bits(s.error);
-}
-
 int aq_fetch_exact(aq_ctx* ctx, int slot, int64_t* row) {
     if (!ctx || !row || slot < 0 || slot >= NSLOTS) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
@@ -982,25 +960,27 @@ int aq_synchronize(aq_ctx* ctx) {
     return AQ_OK;
 }
 
+// A synchronous call: the launch into SYNC_SLOT and its read-back (err: an ERR launch, its sums into *err).
+static int sync_call(aq_ctx* ctx, const aq_problem* p, const double* theta, int shard, int nshards, aq_result* res,
+                     aq_err* err) {
+    LaunchArgs g = sync_args(p, theta, shard, nshards);
+    g.err = err != nullptr;
+    g.sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
+    const int rc = checked_launch(ctx, g, NSLOTS_ALL);
+    return rc ? rc : fetch_sync(ctx, res, err);
+}
+
 int aq_integrate_shard(aq_ctx* ctx, const aq_problem* p, int shard, int nshards, aq_result* res) {
     if (!ctx) return AQ_EINVAL;
-    int rc = validate(p);
-    if (rc) return rc;
-    ctx->sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
-    rc = many_common(ctx, p->integrand, 1, &p->a, &p->b, nullptr, p->eps, p->max_depth, shard, nshards, SYNC_SLOT,
-                     NSLOTS_ALL);
-    ctx->sync_fold = false;
-    if (rc) return rc;
-    return fetch_sync(ctx, res);
+    const int rc = validate(p);
+    return rc ? rc : sync_call(ctx, p, nullptr, shard, nshards, res, nullptr);
 }
 
 int aq_integrate_shard_exact(aq_ctx* ctx, const aq_problem* p, int shard, int nshards, int64_t* row) {
     if (!ctx || !row) return AQ_EINVAL;
     int rc = validate(p);
     if (rc) return rc;
-    rc = many_common(ctx, p->integrand, 1, &p->a, &p->b, nullptr, p->eps, p->max_depth, shard, nshards, SYNC_SLOT,
-                     NSLOTS_ALL);
-    if (rc) return rc;
+    if ((rc = checked_launch(ctx, sync_args(p, nullptr, shard, nshards), NSLOTS_ALL))) return rc;
     // the slot stays marked used: the next launch into it resets it first (ensure_clean)
     return fetch_exact_slot(ctx, SYNC_SLOT, row);
 }
@@ -1011,78 +991,37 @@ int aq_integrate(aq_ctx* ctx, const aq_problem* p, aq_result* res) {
 }
 
 // ---- per-integral parameters (AQ_F_PARAM) -----------------------------------------------------------
-static int many_params_common(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta, double eps,
-                              int max_depth, int shard, int nshards, int first_slot, int slot_limit = NSLOTS) {
-    if (!ctx || k < 1 || k > MAXK || !a || !b || !theta) return AQ_EINVAL;
-    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
-    if (nshards < 1 || nshards > 64 || shard < 0 || shard >= nshards) return AQ_EINVAL;
-    if (first_slot < 0 || first_slot + k > slot_limit) return AQ_EINVAL;
-    for (int i = 0; i < k; ++i)
-        if (!params_ok(a[i], b[i], theta + (size_t)i * param::nparams)) return AQ_EINVAL;
-    AQ_HIP(hipSetDevice(ctx->device));
-    return launch_params(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
-}
-
 int aq_integrate_many_params_async(aq_ctx* ctx, int k, const double* a, const double* b, const double* theta,
                                    double eps, int max_depth, int shard, int nshards, int first_slot) {
-    return many_params_common(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+    return checked_launch(ctx, many_args(AQ_F_PARAM, k, a, b, theta, eps, max_depth, shard, nshards, first_slot));
 }
 
 int aq_integrate_params(aq_ctx* ctx, const aq_problem* p, const double* theta, aq_result* res) {
     if (!ctx || !p || !theta) return AQ_EINVAL;
     if (p->integrand != AQ_F_PARAM || p->n_gpus > 1 || p->n_gpus < 0) return AQ_EINVAL;
-    ctx->sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
-    const int rc = many_params_common(ctx, 1, &p->a, &p->b, theta, p->eps, p->max_depth, 0, 1, SYNC_SLOT, NSLOTS_ALL);
-    ctx->sync_fold = false;
-    if (rc) return rc;
-    return fetch_sync(ctx, res);
+    return sync_call(ctx, p, theta, 0, 1, res, nullptr);
 }
 
 // ---- error estimate (the ERR launches) -----------------------------------------------------------------
 double aq_err_extrapolate(double area, const aq_err* e) { return e ? area + e->err_signed / 3.0 : area; }
 
-// theta goes with AQ_F_PARAM and with nothing else
-static bool err_theta_ok(int integrand, const double* theta) {
-    return integrand == AQ_F_PARAM ? theta != nullptr : (integrand_ok(integrand) && theta == nullptr);
-}
-
-static int many_err_common(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const double* theta,
-                           double eps, int max_depth, int shard, int nshards, int first_slot, int slot_limit = NSLOTS) {
-    if (!ctx || k < 1 || k > MAXK || !a || !b) return AQ_EINVAL;
-    if (!err_theta_ok(integrand, theta)) return AQ_EINVAL;
-    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
-    if (nshards < 1 || nshards > 64 || shard < 0 || shard >= nshards) return AQ_EINVAL;
-    if (first_slot < 0 || first_slot + k > slot_limit) return AQ_EINVAL;
-    for (int i = 0; i < k; ++i)
-        if (theta ? !params_ok(a[i], b[i], theta + (size_t)i * param::nparams) : !bounds_ok(integrand, a[i], b[i]))
-            return AQ_EINVAL;
-    AQ_HIP(hipSetDevice(ctx->device));
-    const int rc = ensure_err(ctx);
-    if (rc) return rc;
-    return theta ? launch_params(ctx, k, a, b, theta, eps, max_depth, shard, nshards, first_slot, nullptr, nullptr, true)
-                 : launch_any(ctx, integrand, k, a, b, nullptr, eps, max_depth, shard, nshards, first_slot, nullptr, true);
-}
-
 int aq_integrate_many_err_async(aq_ctx* ctx, int integrand, int k, const double* a, const double* b, const double* theta,
                                 double eps, int max_depth, int shard, int nshards, int first_slot) {
-    return many_err_common(ctx, integrand, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+    LaunchArgs g = many_args(integrand, k, a, b, theta, eps, max_depth, shard, nshards, first_slot);
+    g.err = true;
+    return checked_launch(ctx, g);
 }
 
 int aq_integrate_err(aq_ctx* ctx, const aq_problem* p, const double* theta, aq_result* res, aq_err* err) {
     if (!ctx || !p || !res || !err) return AQ_EINVAL;
-    if (!err_theta_ok(p->integrand, theta) || p->n_gpus > 1) return AQ_EINVAL;
+    if (!theta_ok(p->integrand, theta) || p->n_gpus > 1) return AQ_EINVAL;
     if (!theta) {
         const int rc = validate(p);
         if (rc) return rc;
     } else if (p->n_gpus < 0) {
         return AQ_EINVAL;
     }
-    ctx->sync_fold = true;   // fetch_sync's k_fetch_sync folds the per-CU area words itself
-    const int rc = many_err_common(ctx, p->integrand, 1, &p->a, &p->b, theta, p->eps, p->max_depth, 0, 1, SYNC_SLOT,
-                                   NSLOTS_ALL);
-    ctx->sync_fold = false;
-    if (rc) return rc;
-    return fetch_sync(ctx, res, err);
+    return sync_call(ctx, p, theta, 0, 1, res, err);
 }
 
 int aq_fetch_err(aq_ctx* ctx, int slot, aq_err* err) {
@@ -1118,56 +1057,26 @@ int aq_group_create(aq_ctx* const* ctxs, int n, aq_group** out) {
             if (d == ctxs[i]->device) return AQ_EINVAL;   // one context per GPU
         devs.push_back(ctxs[i]->device);
     }
-    aq_group* g = new aq_group();
-    g->nranks = n;
+    aq_group* g = new aq_group(n, n);
     g->grid = ctxs[0]->grid;
-    g->comm.resize(n);
     for (int i = 0; i < n; ++i) {
         g->ctx.push_back(ctxs[i]);
         g->rank.push_back(i);
     }
-    ncclResult_t r = ncclCommInitAll(g->comm.data(), n, devs.data());
-    if (r != ncclSuccess) {
-        fprintf(stderr, "aquad: ncclCommInitAll: %s\n", ncclGetErrorString(r));
-        g->comm.clear();
-        aq_group_destroy(g);
-        return AQ_ERCCL;
-    }
-    const int rc = group_alloc(g);
-    if (rc) {
-        aq_group_destroy(g);
-        return rc;
-    }
-    *out = g;
-    return AQ_OK;
+    return group_finish(g, ncclCommInitAll(g->comm.data(), n, devs.data()), "ncclCommInitAll", out);
 }
 
 int aq_group_join(aq_ctx* ctx, int nranks, int rank, const void* id, aq_group** out) {
     if (!ctx || !id || !out || nranks < 1 || rank < 0 || rank >= nranks) return AQ_EINVAL;
     *out = nullptr;
     AQ_HIP(hipSetDevice(ctx->device));
-    aq_group* g = new aq_group();
-    g->nranks = nranks;
+    aq_group* g = new aq_group(nranks, 1);
     g->grid = ctx->grid;
     g->ctx.push_back(ctx);
     g->rank.push_back(rank);
-    g->comm.resize(1);
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
-    ncclResult_t r = ncclCommInitRank(&g->comm[0], nranks, u, rank);
-    if (r != ncclSuccess) {
-        fprintf(stderr, "aquad: ncclCommInitRank: %s\n", ncclGetErrorString(r));
-        g->comm.clear();
-        aq_group_destroy(g);
-        return AQ_ERCCL;
-    }
-    const int rc = group_alloc(g);
-    if (rc) {
-        aq_group_destroy(g);
-        return rc;
-    }
-    *out = g;
-    return AQ_OK;
+    return group_finish(g, ncclCommInitRank(&g->comm[0], nranks, u, rank), "ncclCommInitRank", out);
 }
 
 void aq_group_destroy(aq_group* g) {
@@ -1175,14 +1084,9 @@ void aq_group_destroy(aq_group* g) {
     for (size_t m = 0; m < g->ctx.size(); ++m) {
         (void)hipSetDevice(g->ctx[m]->device);
         (void)hipStreamSynchronize(g->ctx[m]->stream);
-        if (m < g->comm.size() && g->comm[m]) (void)ncclCommDestroy(g->comm[m]);
-        if (m < g->d_sum.size()) (void)hipFree(g->d_sum[m]);
-        if (m < g->d_mine.size()) (void)hipFree(g->d_mine[m]);
-        if (m < g->d_all.size()) (void)hipFree(g->d_all[m]);
+        if (g->comm[m]) (void)ncclCommDestroy(g->comm[m]);
     }
-    if (g->h_sum) (void)hipHostFree(g->h_sum);
-    if (g->h_all) (void)hipHostFree(g->h_all);
-    delete g;
+    delete g;   // (the buffers free themselves: aq_host_mem.h)
 }
 
 int aq_group_size(const aq_group* g) { return g ? g->nranks : 0; }
@@ -1200,10 +1104,10 @@ int aq_integrate_group(aq_group* g, const aq_problem* p, aq_result* res) {
     for (size_t m = 0; m < g->ctx.size(); ++m) {
         aq_ctx* c = g->ctx[m];
         AQ_HIP(hipSetDevice(c->device));
-        c->sync_fold = true;   // k_pack_group folds the per-CU area words itself
-        rc = launch_any(c, p->integrand, 1, &p->a, &p->b, nullptr, p->eps, p->max_depth, g->rank[m], N, SYNC_SLOT);
-        c->sync_fold = false;
-        if (rc) return rc;
+        LaunchArgs la = sync_args(p, nullptr, g->rank[m], N);
+        la.hist = c->histograms;
+        la.sync_fold = true;   // k_pack_group folds the per-CU area words itself
+        if ((rc = launch(c, la))) return rc;
         AQ_HIP(hipMemsetAsync(g->d_sum[m], 0, sizeof(long long) * GROUP_SUM, c->stream));
         hipLaunchKernelGGL(k_pack_group, dim3(1), dim3(256), 0, c->stream, c->d_ctl, c->d_parts,
                            (const double*)c->d_parea, SYNC_SLOT, g->grid, c->parts_dirty[SYNC_SLOT] ? 1 : 0, g->d_sum[m],
@@ -1311,33 +1215,13 @@ int aq_tasks_per_cu(aq_ctx* ctx, uint64_t* out, int cap) {
 }
 
 // The context's two frontier buffers hold at least cap records each. They only grow; a failed
-// allocation leaves neither (front_cap 0), so no caller ever launches on half a pair.
-static void free_front(aq_ctx* ctx) {
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->d_front[i]) {
-            (void)hipFree(ctx->d_front[i]);
-            ctx->dev_bytes -= ctx->front_bytes[i];
-        }
-        ctx->d_front[i] = nullptr;
-        ctx->front_bytes[i] = 0;
-    }
-    ctx->front_cap = 0;
-}
-
+// allocation leaves neither, so the two always hold the same count and no caller launches on half a pair.
 static int ensure_front(aq_ctx* ctx, size_t cap) {
-    if (ctx->d_front[0] && ctx->d_front[1] && ctx->front_cap >= cap) return AQ_OK;
-    free_front(ctx);
-    for (int i = 0; i < 2; ++i) {
-        const int rc = dmalloc(ctx, &ctx->d_front[i], cap * sizeof(Rec), false);
-        if (rc) {
-            ctx->d_front[i] = nullptr;
-            free_front(ctx);
-            return rc;
-        }
-        ctx->front_bytes[i] = cap * sizeof(Rec);
-    }
-    ctx->front_cap = cap;
-    return AQ_OK;
+    if (ctx->d_front[0].grow(cap) == hipSuccess && ctx->d_front[1].grow(cap) == hipSuccess) return AQ_OK;
+    ctx->d_front[0].reset();
+    ctx->d_front[1].reset();
+    fprintf(stderr, "aquad: no device memory for two frontier buffers of %zu records\n", cap);
+    return AQ_EHIP;
 }
 
 int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64_t* tpl, uint64_t* lpl,
@@ -1349,6 +1233,7 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
     const int max_depth = p->max_depth ? p->max_depth : AQ_DEFAULT_MAX_DEPTH;
     // 16 M records (512 MiB) per buffer at least, whatever a frontier run left there before
     if ((rc = ensure_front(ctx, (size_t)1 << 24))) return rc;
+    const size_t front_cap = ctx->d_front[0].count();
     DevResults* dres = ctx->d_lres;
     AQ_HIP(hipMemsetAsync(dres, 0, sizeof(DevResults), ctx->stream));
     AQ_HIP(hipMemsetAsync(ctx->d_count, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
@@ -1366,14 +1251,14 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
         const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
         with_fid(p->integrand, [&](auto F) {
             hipLaunchKernelGGL((k_level<decltype(F)::value>), dim3(grid), dim3(256), 0, ctx->stream, in, n, outb, n_out,
-                               (unsigned)ctx->front_cap, p->eps, depth, max_depth, dres, ctx->d_tab);
+                               (unsigned)front_cap, p->eps, depth, max_depth, dres, ctx->d_tab);
         });
         AQ_HIP(hipGetLastError());
         AQ_HIP(hipMemcpyAsync(ctx->h_lres, n_out, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
         AQ_HIP(hipStreamSynchronize(ctx->stream));
         unsigned next = 0;
         memcpy(&next, ctx->h_lres, sizeof(unsigned));
-        if (next > ctx->front_cap) next = (unsigned)ctx->front_cap;  // overflow flagged in res->error
+        if (next > front_cap) next = (unsigned)front_cap;  // overflow flagged in res->error
         n = next;
     }
     AQ_HIP(hipMemcpyAsync(ctx->h_lres, dres, sizeof(DevResults), hipMemcpyDeviceToHost, ctx->stream));
@@ -1400,13 +1285,8 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
 }
 
 static int ensure_eval(aq_ctx* ctx, size_t n) {
-    if (ctx->eval_cap >= n) return AQ_OK;
-    (void)hipFree(ctx->d_x);
-    (void)hipFree(ctx->d_y);
-    ctx->d_x = ctx->d_y = nullptr;
-    AQ_HIP(hipMalloc(&ctx->d_x, n * sizeof(double)));
-    AQ_HIP(hipMalloc(&ctx->d_y, n * sizeof(double)));
-    ctx->eval_cap = n;
+    AQ_HIP(ctx->d_x.grow(n));
+    AQ_HIP(ctx->d_y.grow(n));
     return AQ_OK;
 }
 
@@ -1470,31 +1350,6 @@ int aq_eval_integrand_params(aq_ctx* ctx, size_t n, const double* x, const doubl
 static int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e && *e ? atoi(e) : dflt;
-}
-
-// Chunk sizes of an n-integral batch: a first chunk of `first`, each next one twice the last up to
-// MAXK (a chunk's launch then covers the host's checks and staging of the next, ~1.8 ns per integral
-// against ~5 ns of kernel), the remainder last -- split so the last chunk is `last` when the remainder
-// is large. AQ_BATCH_FIRST / AQ_BATCH_LAST in the environment override the defaults (0: no small
-// first / last chunk).
-static std::vector<int> batch_chunks(size_t n) {
-    const size_t first = (size_t)std::max(0, env_int("AQ_BATCH_FIRST", AQ_BATCH_FIRST));
-    const size_t last = (size_t)std::max(0, env_int("AQ_BATCH_LAST", AQ_BATCH_LAST));
-    std::vector<int> c;
-    size_t done = 0, next = first ? std::min(first, (size_t)MAXK) : (size_t)MAXK;
-    while (n - done > next) {
-        c.push_back((int)next);
-        done += next;
-        next = std::min(2 * next, (size_t)MAXK);
-    }
-    const size_t rem = n - done;
-    if (last && rem > 2 * last) {
-        c.push_back((int)(rem - last));
-        c.push_back((int)last);
-    } else if (rem) {
-        c.push_back((int)rem);
-    }
-    return c;
 }
 
 // f(lo, hi, part) over [0, n) in up to 64 contiguous pieces, on the context's host pool and the caller:
@@ -1561,116 +1416,60 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count());
     };
     AQ_HIP(hipSetDevice(ctx->device));
-    int rc;
-    const std::vector<int> chunks = batch_chunks(n);
+    const std::vector<int> chunks = batch_chunks(n, (size_t)std::max(0, env_int("AQ_BATCH_FIRST", AQ_BATCH_FIRST)),
+                                                 (size_t)std::max(0, env_int("AQ_BATCH_LAST", AQ_BATCH_LAST)));
     const size_t nc = chunks.size();
     const size_t rows = (size_t)*std::max_element(chunks.begin(), chunks.end());   // <= MAXK
-    if (ctx->bdev_rows < rows) {
-        auto dfree = [&](void* p, size_t bytes) {
-            if (p) { (void)hipFree(p); ctx->dev_bytes -= bytes; }
-        };
-        const size_t r0 = ctx->bdev_rows;
-        dfree(ctx->d_batch, sizeof(double) * 8 * r0);
-        dfree(ctx->d_bbounds, sizeof(double2) * 2 * r0);
-        dfree(ctx->d_bsorted, sizeof(double2) * 2 * r0);
-        dfree(ctx->d_bkey, sizeof(unsigned) * r0);
-        dfree(ctx->d_bperm, sizeof(unsigned) * 2 * r0);
-        ctx->d_batch = nullptr;
-        ctx->d_bbounds = ctx->d_bsorted = nullptr;
-        ctx->d_bkey = ctx->d_bperm = nullptr;
-        ctx->bdev_rows = 0;
-        if ((rc = dmalloc(ctx, &ctx->d_batch, sizeof(double) * 8 * rows, false))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->d_bbounds, sizeof(double2) * 2 * rows, false))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->d_bsorted, sizeof(double2) * 2 * rows, false))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->d_bkey, sizeof(unsigned) * rows, false))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->d_bperm, sizeof(unsigned) * 2 * rows, false))) return rc;
-        ctx->bdev_rows = rows;
-    }
-    if (ctx->bhost_cap < n) {
-        if (ctx->h_batch) AQ_HIP(hipHostFree(ctx->h_batch));
-        if (ctx->h_bbounds) AQ_HIP(hipHostFree(ctx->h_bbounds));
-        ctx->h_batch = nullptr;
-        ctx->h_bbounds = nullptr;
-        ctx->bhost_cap = 0;
-        AQ_HIP(hipHostMalloc(&ctx->h_batch, sizeof(double) * 4 * n, hipHostMallocDefault));
-        AQ_HIP(hipHostMalloc(&ctx->h_bbounds, sizeof(double2) * n, hipHostMallocDefault));
-        ctx->bhost_cap = n;
-    }
+    // the device rings hold two chunks of `rows`, the pinned copies the whole call (grow-only, aq_ctx)
+    AQ_HIP(ctx->d_batch.grow(8 * rows));
+    AQ_HIP(ctx->d_bbounds.grow(2 * rows));
+    AQ_HIP(ctx->d_bsorted.grow(2 * rows));
+    AQ_HIP(ctx->d_bkey.grow(rows));
+    AQ_HIP(ctx->d_bperm.grow(2 * rows));
+    AQ_HIP(ctx->h_batch.grow(4 * n));
+    AQ_HIP(ctx->h_bbounds.grow(n));
     if (par) {
-        if ((rc = ensure_params(ctx))) return rc;
-        if (ctx->btheta_rows < rows) {
-            const size_t r0 = ctx->btheta_rows;
-            if (ctx->d_btheta) { (void)hipFree(ctx->d_btheta); ctx->dev_bytes -= sizeof(double) * NP * 2 * r0; }
-            if (ctx->d_bthsorted) { (void)hipFree(ctx->d_bthsorted); ctx->dev_bytes -= sizeof(double) * NP * 2 * r0; }
-            ctx->d_btheta = ctx->d_bthsorted = nullptr;
-            ctx->btheta_rows = 0;
-            if ((rc = dmalloc(ctx, &ctx->d_btheta, sizeof(double) * NP * 2 * rows, false))) return rc;
-            if ((rc = dmalloc(ctx, &ctx->d_bthsorted, sizeof(double) * NP * 2 * rows, false))) return rc;
-            ctx->btheta_rows = rows;
-        }
-        if (ctx->btheta_hcap < n) {
-            if (ctx->h_btheta) AQ_HIP(hipHostFree(ctx->h_btheta));
-            ctx->h_btheta = nullptr;
-            ctx->btheta_hcap = 0;
-            AQ_HIP(hipHostMalloc(&ctx->h_btheta, sizeof(double) * NP * n, hipHostMallocDefault));
-            ctx->btheta_hcap = n;
-        }
+        AQ_HIP(ctx->d_btheta.grow(NP * 2 * rows));
+        AQ_HIP(ctx->d_bthsorted.grow(NP * 2 * rows));
+        AQ_HIP(ctx->h_btheta.grow(NP * n));
     }
     if (err) {
-        if ((rc = ensure_err(ctx))) return rc;
-        if (ctx->berr_rows < rows) {
-            if (ctx->d_berr) { (void)hipFree(ctx->d_berr); ctx->dev_bytes -= sizeof(double) * 4 * ctx->berr_rows; }
-            ctx->d_berr = nullptr;
-            ctx->berr_rows = 0;
-            if ((rc = dmalloc(ctx, &ctx->d_berr, sizeof(double) * 4 * rows, false))) return rc;
-            ctx->berr_rows = rows;
-        }
-        if (ctx->berr_hcap < n) {
-            if (ctx->h_berr) AQ_HIP(hipHostFree(ctx->h_berr));
-            ctx->h_berr = nullptr;
-            ctx->berr_hcap = 0;
-            AQ_HIP(hipHostMalloc(&ctx->h_berr, sizeof(double) * 2 * n, hipHostMallocDefault));
-            ctx->berr_hcap = n;
-        }
+        AQ_HIP(ctx->d_berr.grow(4 * rows));
+        AQ_HIP(ctx->h_berr.grow(2 * n));
     }
-    auto dev_err_rows_of = [&](size_t c) { return ctx->d_berr + 2 * (c & 1u) * ctx->berr_rows; };
-    const size_t RT = ctx->btheta_rows;
-    auto dev_theta_of = [&](size_t c) { return ctx->d_btheta + (c & 1u) * RT * NP; };
-    auto thsorted_of = [&](size_t c) { return ctx->d_bthsorted + (c & 1u) * RT * NP; };
-    // chunk c's device rings: bounds, rows and the size order at parity c & 1 (the keys live only
-    // between a chunk's two pre-pass kernels, which run in order on s_pre)
-    const size_t R = ctx->bdev_rows;
+    // chunk c's device rings: bounds, rows, theta, error sums and the size order at parity c & 1, this call's
+    // `rows` apart (every ring holds at least that; the keys live only between a chunk's two pre-pass
+    // kernels, which run in order on s_pre)
+    const size_t R = rows;
+    auto dev_err_rows_of = [&](size_t c) { return ctx->d_berr + 2 * (c & 1u) * R; };
+    auto dev_theta_of = [&](size_t c) { return ctx->d_btheta + (c & 1u) * R * NP; };
+    auto thsorted_of = [&](size_t c) { return ctx->d_bthsorted + (c & 1u) * R * NP; };
     auto dev_bounds_of = [&](size_t c) { return ctx->d_bbounds + (c & 1u) * R; };
     auto dev_rows_of = [&](size_t c) { return ctx->d_batch + 4 * (c & 1u) * R; };
     auto sorted_of = [&](size_t c) { return ctx->d_bsorted + (c & 1u) * R; };
     auto perm_of = [&](size_t c) { return ctx->d_bperm + (c & 1u) * R; };
     // size classes: counts + cursors per chunk parity (k_batch_scatter zeroes the other parity's)
-    if (!ctx->d_bcnt && (rc = dmalloc(ctx, &ctx->d_bcnt, sizeof(unsigned) * 4 * EST_KEYS, false))) return rc;
-    if (!ctx->d_best && (rc = dmalloc(ctx, &ctx->d_best, sizeof(double) * 2, false))) return rc;
+    AQ_HIP(ctx->d_bcnt.grow(4 * EST_KEYS));
+    AQ_HIP(ctx->d_best.grow(2));
     // chunks in size order (largest trees first: the launch's tail is its smallest jobs), unless
     // AQ_BATCH_SORT=0; chunks small enough for the per-CU instance keep their order (their bounds
     // travel as kernel arguments)
     const bool sort = env_int("AQ_BATCH_SORT", 1) != 0;
-    if (!ctx->s_h2d) AQ_HIP(hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking));
-    if (!ctx->s_d2h) AQ_HIP(hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking));
-    if (!ctx->s_pre) AQ_HIP(hipStreamCreateWithFlags(&ctx->s_pre, hipStreamNonBlocking));
+    for (Stream* s : {&ctx->s_h2d, &ctx->s_d2h, &ctx->s_pre})
+        if (!*s) AQ_HIP(s->create());
     std::vector<size_t> off(nc + 1, 0);
     for (size_t c = 0; c < nc; ++c) off[c + 1] = off[c] + (size_t)chunks[c];
     // four events per chunk: bounds on the device, rows gathered, rows on the host, size order done;
     // and one for the work already on the context's stream (the pre-pass stream starts behind it: a
-    // caller's pending launch updates the job-size hint the first pre-pass may preset)
-    std::vector<hipEvent_t> ev(4 * nc + 1, nullptr);
-    for (auto& e : ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            for (auto& f : ev)
-                if (f) (void)hipEventDestroy(f);
-            return AQ_EHIP;
-        }
-    auto ev_h2d = [&](size_t c) { return ev[4 * c]; };
-    auto ev_gath = [&](size_t c) { return ev[4 * c + 1]; };
-    auto ev_d2h = [&](size_t c) { return ev[4 * c + 2]; };
-    auto ev_pre = [&](size_t c) { return ev[4 * c + 3]; };
-    const hipEvent_t ev_start = ev[4 * nc];
+    // caller's pending launch updates the job-size hint the first pre-pass may preset), and one behind the
+    // zeroing of the size-class counts. (Destroyed on return, after every stream was synchronised.)
+    std::vector<Event> ev(4 * nc + 2);
+    for (Event& e : ev) AQ_HIP(e.create(hipEventDisableTiming));
+    auto ev_h2d = [&](size_t c) -> hipEvent_t { return ev[4 * c]; };
+    auto ev_gath = [&](size_t c) -> hipEvent_t { return ev[4 * c + 1]; };
+    auto ev_d2h = [&](size_t c) -> hipEvent_t { return ev[4 * c + 2]; };
+    auto ev_pre = [&](size_t c) -> hipEvent_t { return ev[4 * c + 3]; };
+    const hipEvent_t ev_start = ev[4 * nc], ev_zero = ev[4 * nc + 1];
     unsigned errbits = 0;
     std::vector<char> sorted_chunk(nc, 0);
     // rows [i0, i1) into the outputs (k_gather_reset wrote size-ordered slots back in order)
@@ -1711,15 +1510,17 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
     // between the two operations (profiles/r06o: copy -> estimate 18 us, scatter -> launch 17 us,
     // gather -> last copy back 62 us, against ~7 us in order). The middle chunks' keep their own
     // streams, whose work overlaps the previous launch.
-    auto h2d_stream = [&](size_t c) { return c == 0 ? ctx->stream : ctx->s_h2d; };
-    auto pre_stream = [&](size_t c) { return c == 0 ? ctx->stream : ctx->s_pre; };
-    auto d2h_stream = [&](size_t c) { return c + 1 == nc ? ctx->stream : ctx->s_d2h; };
+    auto h2d_stream = [&](size_t c) -> hipStream_t { return c == 0 ? ctx->stream : ctx->s_h2d; };
+    auto pre_stream = [&](size_t c) -> hipStream_t { return c == 0 ? ctx->stream : ctx->s_pre; };
+    auto d2h_stream = [&](size_t c) -> hipStream_t { return c + 1 == nc ? ctx->stream : ctx->s_d2h; };
     auto order = [&](size_t c, bool preset) -> int {
         const int m = chunks[c];
         const hipStream_t sp = pre_stream(c);
         if (hipStreamWaitEvent(sp, ev_h2d(c), 0) != hipSuccess) return AQ_EHIP;
-        // (chunk 1's estimate adds into the counts chunk 0's scatter zeroed, on the context's stream)
-        if (c == 1 && sorted_at(0) && hipStreamWaitEvent(sp, ev_pre(0), 0) != hipSuccess) return AQ_EHIP;
+        // (chunk 1's estimate adds into the counts chunk 0's scatter zeroed, on the context's stream -- or,
+        // behind an unsorted chunk 0, into the counts the call zeroed there: ev_zero. Later chunks follow
+        // both through ev_gath(c - 2), which their bounds' copy waited for)
+        if (c == 1 && hipStreamWaitEvent(sp, sorted_at(0) ? ev_pre(0) : ev_zero, 0) != hipSuccess) return AQ_EHIP;
         const unsigned blocks = (unsigned)((m + 255) / 256);
         unsigned* const cnt = ctx->d_bcnt + 2 * EST_KEYS * (c & 1u);
         unsigned* const cnt_next = ctx->d_bcnt + 2 * EST_KEYS * ((c + 1) & 1u);
@@ -1772,18 +1573,18 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
             return AQ_EHIP;
         return AQ_OK;
     };
-    const bool hist = ctx->histograms;
-    ctx->histograms = false;
     size_t ran = 0;   // chunks enqueued
-    rc = AQ_OK;
-    // (the counts are zeroed on s_pre, ahead of the first estimate, once the work already queued on the
-    // context's stream is done -- a pending launch may still read or write the hint the first scatter
-    // may preset)
+    int rc = AQ_OK;
+    // (s_pre starts once the work already queued on the context's stream is done -- a pending launch may
+    // still read or write the hint the first scatter may preset. The counts are zeroed on the context's
+    // stream, where chunk 0's pre-pass runs; behind an unsorted chunk 0 the first pre-pass is chunk 1's on
+    // s_pre, which waits for ev_zero: order)
     if (hipEventRecord(ev_start, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->s_pre, ev_start, 0) != hipSuccess)
         rc = AQ_EHIP;
     if (rc == AQ_OK && sort &&
         (hipMemsetAsync(ctx->d_bcnt, 0, sizeof(unsigned) * 4 * EST_KEYS, pre_stream(0)) != hipSuccess ||
-         hipMemsetAsync(ctx->d_best, 0, sizeof(double) * 2, pre_stream(0)) != hipSuccess))
+         hipMemsetAsync(ctx->d_best, 0, sizeof(double) * 2, pre_stream(0)) != hipSuccess ||
+         (!sorted_at(0) && hipEventRecord(ev_zero, pre_stream(0)) != hipSuccess)))
         rc = AQ_EHIP;
     mark("setup", -1);
     if (rc == AQ_OK) rc = stage(0);
@@ -1796,14 +1597,18 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
             rc = AQ_EHIP;
             break;
         }
+        LaunchArgs g;   // (no histograms: hist stays false)
+        g.integrand = integrand;
+        g.k = m;
+        g.a = a + off[c];
+        g.b = b + off[c];
+        g.eps = eps;
+        g.dev_bounds = sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c);
+        if (par) g.dev_theta = sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c);
+        g.err = err;
+        g.heap = true;
         ctx->hint.preset = preset_at(c);
-        ctx->batch_heap = true;
-        rc = par ? launch_params(ctx, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
-                                 sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c),
-                                 sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c), err)
-                 : launch_any(ctx, integrand, m, a + off[c], b + off[c], nullptr, eps, 0, 0, 1, 0,
-                              sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c), err);
-        ctx->batch_heap = false;
+        rc = launch(ctx, g);
         ctx->hint.preset = false;
         mark("launched", (long)c);
         if (rc) break;
@@ -1844,13 +1649,11 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
         }
         rc = rc_next;
     }
-    ctx->histograms = hist;
     // every enqueued chunk finishes before the buffers can be reused or the events destroyed
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
     if (hipStreamSynchronize(ctx->s_d2h) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
     if (hipStreamSynchronize(ctx->s_h2d) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
     if (hipStreamSynchronize(ctx->s_pre) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
-    for (auto& e : ev) (void)hipEventDestroy(e);
     mark("device done", -1);
     if (rc) return rc;
     if (ran) unpack(ran - 1);
@@ -1878,7 +1681,7 @@ int aq_integrate_batch_params(aq_ctx* ctx, size_t n, const double* a, const doub
 int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
                            int integrand, double* area, uint64_t* accepted, uint64_t* tasks, double* err_abs,
                            double* err_signed) {
-    if (!ctx || !err_theta_ok(integrand, theta)) return AQ_EINVAL;
+    if (!ctx || !theta_ok(integrand, theta)) return AQ_EINVAL;
     return batch_run(ctx, n, a, b, theta, eps, integrand, area, accepted, tasks, true, err_abs, err_signed);
 }
 
@@ -1914,7 +1717,7 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
     int rc;
-    if (!ctx->d_lparts && (rc = dmalloc(ctx, &ctx->d_lparts, sizeof(LevelPart) * LP_CAP, false))) return rc;
+    AQ_HIP(ctx->d_lparts.grow(LP_CAP));
     if (!d_n_in) AQ_HIP(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), ctx->stream));
     if (n_in == 0) return AQ_OK;
     const int grid = (int)std::min<size_t>(((size_t)n_in + LEVEL_T * LEVEL_R - 1) / (LEVEL_T * LEVEL_R), (size_t)MAXB);
@@ -1979,12 +1782,12 @@ int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sy
     AQ_HIP(hipSetDevice(ctx->device));
     const int max_depth = p->max_depth ? p->max_depth : AQ_DEFAULT_MAX_DEPTH;
     if ((rc = ensure_front(ctx, cap))) return rc;
-    if (!ctx->d_facc && (rc = dmalloc(ctx, &ctx->d_facc, sizeof(double) * 8, false))) return rc;
-    if (!ctx->h_fcount) AQ_HIP(hipHostMalloc(&ctx->h_fcount, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipHostMallocDefault));
-    if (!ctx->h_facc) AQ_HIP(hipHostMalloc(&ctx->h_facc, sizeof(double) * 8, hipHostMallocDefault));
+    AQ_HIP(ctx->d_facc.grow(8));
+    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
+    AQ_HIP(ctx->h_facc.grow(8));
     unsigned* cnt = ctx->d_count;
     double* acc = ctx->d_facc;
-    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0]), reinterpret_cast<double*>(ctx->d_front[1])};
+    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
     AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
     AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
     AQ_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cnt), 1, 1, ctx->stream));   // counts[0] = the root
@@ -2049,7 +1852,7 @@ int aq_kernel_timing(aq_ctx* ctx, int enable) {
     if (!ctx) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
     AQ_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto& e : ctx->ev_pending) ctx->ev_free.push_back(e);
+    for (auto& e : ctx->ev_pending) ctx->ev_free.push_back(std::move(e));
     ctx->ev_pending.clear();
     ctx->timing = enable != 0;
     ctx->timed_ms = 0.0;
@@ -2066,7 +1869,7 @@ int aq_kernel_time(aq_ctx* ctx, double* total_ms, uint64_t* launches) {
         AQ_HIP(hipEventElapsedTime(&ms, e.first, e.second));
         ctx->timed_ms += ms;
         ctx->timed_launches += 1;
-        ctx->ev_free.push_back(e);
+        ctx->ev_free.push_back(std::move(e));
     }
     ctx->ev_pending.clear();
     if (total_ms) *total_ms = ctx->timed_ms;

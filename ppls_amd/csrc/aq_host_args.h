@@ -1,0 +1,61 @@
+// aq_host_args.h -- the C ABI's argument rules that need no device: the range rules every launch entry point
+// shares, the slot-range rule of the gathers, the error code of a slot's error bits, and the batch front
+// end's chunk schedule. aq_abi.inc adds the integrands' domain predicates (they need the plug-ins).
+//
+// Plain host C++17, no HIP: the CPU tests build it with g++ (tests/test_host_args.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <vector>
+
+#include "aquad.h"
+#include "aq_shape.h"
+
+namespace aq {
+
+// a slot's error bits (aq_device.h ERRB_*: aq_abi.inc asserts that they agree)
+constexpr unsigned HB_TIMEOUT = 1, HB_OVERFLOW = 2, HB_DEPTH = 4;
+
+inline int err_from_bits(unsigned bits) {
+    if (bits & HB_TIMEOUT) return AQ_ETIMEOUT;
+    if (bits & HB_OVERFLOW) return AQ_EOVERFLOW;
+    if (bits & HB_DEPTH) return AQ_EDEPTH;
+    return AQ_OK;
+}
+
+inline bool slot_range_ok(int first, int n) { return first >= 0 && n >= 0 && n <= NSLOTS && first < NSLOTS; }
+
+// One launch of k integrals into slots [first_slot, first_slot + k) below slot_limit, as shard `shard` of
+// nshards (shard_array: every integral names its own shard, checked by the caller; `shard` is unused).
+inline bool launch_ranges_ok(int k, double eps, int max_depth, int shard, int nshards, bool shard_array, int first_slot,
+                             int slot_limit) {
+    if (k < 1 || k > MAXK) return false;
+    if (!(eps >= 0.0) || max_depth < 0 || max_depth > AQ_MAX_LEVELS - 1) return false;
+    if (nshards < 1 || nshards > 64) return false;
+    if (!shard_array && (shard < 0 || shard >= nshards)) return false;
+    return first_slot >= 0 && first_slot <= slot_limit - k;
+}
+
+// Chunk sizes of an n-integral batch: a first chunk of `first`, each next one twice the last up to
+// MAXK (a chunk's launch then covers the host's checks and staging of the next, ~1.8 ns per integral
+// against ~5 ns of kernel), the remainder last -- split so the last chunk is `last` when the remainder
+// is large. 0: no small first / last chunk.
+inline std::vector<int> batch_chunks(size_t n, size_t first, size_t last) {
+    std::vector<int> c;
+    size_t done = 0, next = first ? std::min(first, (size_t)MAXK) : (size_t)MAXK;
+    while (n - done > next) {
+        c.push_back((int)next);
+        done += next;
+        next = std::min(2 * next, (size_t)MAXK);
+    }
+    const size_t rem = n - done;
+    if (last && rem > 2 * last) {
+        c.push_back((int)(rem - last));
+        c.push_back((int)last);
+    } else if (rem) {
+        c.push_back((int)rem);
+    }
+    return c;
+}
+
+}  // namespace aq

@@ -244,6 +244,19 @@ def test_batch_front_end_multi_chunk(ctx, batch_golden, oracle):
     assert list(acc2) == list(acc[:64])
 
 
+def test_batch_small_first_chunk_twice(ctx, oracle, monkeypatch):
+    """AQ_BATCH_FIRST=32: chunks [32, 64, 104] of 200 integrals, so chunk 0 runs unsorted and chunk 1's size
+    pre-pass is the call's first -- on its own stream, behind the zeroing of the size-class counts.
+    Two calls on one context, the second meeting the counts the first left: both equal the oracle."""
+    monkeypatch.setenv("AQ_BATCH_FIRST", "32")
+    a, b = oracle.batch_bounds(200)
+    oa, ot, ol = oracle.integrate_batch(a, b, 1e-3)
+    for call in range(2):
+        area, tasks, acc = ctx.integrate_batch(a, b, 1e-3)
+        assert list(acc) == list(ol) and list(tasks) == list(ot), call
+        assert np.all(np.abs(area - oa) <= AREA_RTOL * np.abs(oa)), call
+
+
 def test_cli_reference_output(trees):
     from ppls_amd import build
     build.build()

@@ -7,8 +7,9 @@ the addresses and the pc-relative displacement of globals (s_getpc_b64 + s_add_u
 which move with code placement), and compares every kernel of PARENT with its twin in NEW. --appended
 names the mangled template arguments a change appended to k_stream's list with a default (one defaulted
 bool: Lb0E), so that PARENT's k_stream<...> finds NEW's k_stream<..., false>. Then prints, from NEW's code
-object metadata, VGPRs / SGPRs / scratch / LDS / workgroup size of the k_stream instances PARENT does not
-have. Exit status 1 if any instruction stream differs.
+object metadata, VGPRs / SGPRs / scratch / LDS / workgroup size of the kernels PARENT does not have (`new:`
+lines, kernels of any name). Exit status 1 if any instruction stream differs or NEW holds a kernel that
+PARENT lacks: a change that means to add none passes only when the two sets are equal in both directions.
 """
 import argparse
 import os
@@ -93,12 +94,13 @@ def main():
             print("DIFFERS", demangle(name), where if new is None else (where, ins[where:where + 1], new[where:where + 1]))
     print("k_stream instances identical: %d different: %d" % (same[True], same[False]))
     print("other kernels identical: %d different: %d" % (other[True], other[False]))
-    for name in sorted(n for n in N if "k_stream" in n and n not in twins):
+    added = sorted(n for n in N if n not in twins)   # kernels of NEW without a twin in PARENT, of any name
+    for name in added:
         m = meta.get(name, {})
         print("new:", demangle(name), "vgpr", m.get("vgpr_count"), "sgpr", m.get("sgpr_count"), "scratch",
               m.get("private_segment_fixed_size"), "lds", m.get("group_segment_fixed_size"), "workgroup",
               m.get("max_flat_workgroup_size"))
-    sys.exit(1 if same[False] or other[False] else 0)
+    sys.exit(1 if same[False] or other[False] or added else 0)
 
 
 if __name__ == "__main__":
