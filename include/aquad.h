@@ -37,6 +37,7 @@ extern "C" {
 #define AQ_ERCCL (-8)      /* an RCCL call failed (aq_group_*) */
 #define AQ_ERESIDENT (-9)  /* the persistent grid cannot be co-resident on the device (its workgroups wait
                             on each other): refused before launch, never a stall */
+#define AQ_ENOCONV (-10)   /* some integral missed its tolerance within max_rounds (outputs are still all written) */
 
 #define AQ_DEFAULT_MAX_DEPTH 96
 #define AQ_MAX_LEVELS 128     /* length of the per-level histograms */
@@ -320,6 +321,46 @@ int aq_fetch_err(aq_ctx *ctx, int slot, aq_err *err);
 int aq_integrate_batch_err(aq_ctx *ctx, size_t n, const double *a, const double *b, const double *theta, double eps,
                            int integrand, double *area, uint64_t *accepted, uint64_t *tasks, double *err_abs,
                            double *err_signed);
+
+/* ---- tolerance-driven batch: epsabs / epsrel on the result ---------------------------------------
+ * aq_integrate_batch_tol integrates n integrals of one integrand until each one's error estimate meets the
+ * caller's tolerance: rounds of ERR launches at a shrinking EPSILON, every round over the integrals that
+ * have not retired yet. Round r runs at eps_r (eps_1 = eps0, eps_{r+1} = eps_r / shrink: one division per
+ * round, so a caller reproduces the schedule bit for bit); one EPSILON per round because EPSILON is an
+ * argument of the launch. After a round an integral is CONVERGED when, evaluated in double exactly so,
+ *     err_abs <= fmax(epsabs, epsrel * fabs(area))
+ * (a tie converges; a NaN in err_abs or area does not). An integral retires when it converges, when its row
+ * carries error bits (it is not relaunched), or in round max_rounds. The test, the retiring rows' records
+ * and the stable compaction of the survivors' bounds and parameters run on the device between two launches;
+ * the host reads one count per round. err_abs is the device's sum, schedule-dependent within
+ * accepted * 2^-52 * err_abs (above): a decision nearer to its target than that may go either way from
+ * run to run.
+ * Outputs (any may be NULL; accepted BEFORE tasks, as aq_integrate_batch_err): every integral reports the
+ * area, counts and sums of the round in which it retired, eps_used[i] that round's EPSILON, and
+ * rounds[i] = r (1-based) when it converged in round r, -r when it retired in round r without converging
+ * (r == max_rounds, or its row carried error bits).
+ * Returns the code of the rows' error bits if any row had some (AQ_ETIMEOUT, AQ_EOVERFLOW, AQ_EDEPTH), else
+ * AQ_ENOCONV if an integral did not converge -- the outputs are all written in both cases -- else AQ_OK.
+ * AQ_EINVAL: a bad aq_tol (below; also when the last round's EPSILON would no longer be a normal double), a
+ * theta that does not go with the integrand (as the _err calls), a bad bound or parameter row (checked block
+ * by block as the batch front end checks chunk by chunk: the outputs are then unspecified).
+ * The call blocks. The integrals run in blocks of up to aq_max_integrals_per_launch() (AQ_TOL_BLOCK=<n> in
+ * the environment, read per call, sets a smaller block), every round's launch into slots 0 .. k-1, which the
+ * call leaves clean; rows run in compacted input order (no size order). Its device buffers are allocated by
+ * the first of these calls.
+ * Not covered: shards, aq_group, aq_integrate_mixed_async, aq_integrate_levels and the frontier engine. */
+typedef struct {
+    double epsabs, epsrel;  /* converged when err_abs <= fmax(epsabs, epsrel * fabs(area)); both >= 0, finite, not both 0 */
+    double eps0;            /* EPSILON of round 1; finite, > 0 */
+    double shrink;          /* eps of round r+1 = eps of round r / shrink (one division per round); 0 -> 8; else in [2, 1024] */
+    int32_t max_rounds;     /* 0 -> 12; else 1..64 */
+    int32_t max_depth;      /* as aq_problem.max_depth */
+} aq_tol;
+int aq_integrate_batch_tol(aq_ctx *ctx, size_t n, const double *a, const double *b, const double *theta,
+                           int integrand, const aq_tol *tol,
+                           double *area, uint64_t *accepted, uint64_t *tasks,
+                           double *err_abs, double *err_signed,
+                           double *eps_used, int32_t *rounds);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel on the context's

@@ -15,6 +15,7 @@ from .aquad import (  # noqa: F401
     Group,
     Problem,
     Result,
+    TolResult,
     exact_round,
     farmer,
     format_reference,
@@ -24,5 +25,6 @@ from .aquad import (  # noqa: F401
     user_integrand_name,
 )
 
-__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "Group", "Problem", "Result", "exact_round",
+__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "Group", "Problem", "Result", "TolResult",
+           "exact_round",
            "farmer", "format_reference", "integrate", "param_count", "param_integrand_name", "user_integrand_name"]

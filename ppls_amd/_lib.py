@@ -23,6 +23,7 @@ EXPORTS = (
     "aq_param_count", "aq_param_integrand_name", "aq_eval_integrand_params", "aq_integrate_params",
     "aq_integrate_many_params_async", "aq_integrate_batch_params",
     "aq_err_extrapolate", "aq_integrate_err", "aq_integrate_many_err_async", "aq_fetch_err", "aq_integrate_batch_err",
+    "aq_integrate_batch_tol",
 )
 
 AQ_MAX_LEVELS = 128
@@ -31,6 +32,7 @@ AQ_XS_LIMBS = 68
 AQ_EXACT_ROW = AQ_XS_LIMBS + 4
 AQ_GROUP_ID_BYTES = 128
 AQ_MAX_PARAMS = 4
+AQ_ENOCONV = -10
 
 
 class aq_problem(ctypes.Structure):
@@ -48,6 +50,11 @@ class aq_result(ctypes.Structure):
 
 class aq_err(ctypes.Structure):
     _fields_ = [("err_abs", ctypes.c_double), ("err_signed", ctypes.c_double)]
+
+
+class aq_tol(ctypes.Structure):
+    _fields_ = [("epsabs", ctypes.c_double), ("epsrel", ctypes.c_double), ("eps0", ctypes.c_double),
+                ("shrink", ctypes.c_double), ("max_rounds", ctypes.c_int32), ("max_depth", ctypes.c_int32)]
 
 
 _lib = None
@@ -133,6 +140,8 @@ def load(build_if_missing=True):
         "aq_integrate_many_err_async": ([vp, c_int, c_int, dp, dp, dp, c_dbl, c_int, c_int, c_int, c_int], c_int),
         "aq_fetch_err": ([vp, c_int, E], c_int),
         "aq_integrate_batch_err": ([vp, ctypes.c_size_t, dp, dp, dp, c_dbl, c_int, dp, up, up, dp, dp], c_int),
+        "aq_integrate_batch_tol": ([vp, ctypes.c_size_t, dp, dp, dp, c_int, ctypes.POINTER(aq_tol), dp, up, up, dp, dp,
+                                    dp, ip], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -70,6 +70,17 @@ class Result:
     area_extrapolated: Optional[float] = None
 
 
+class TolResult(tuple):
+    """Context.integrate_batch_tol's seven arrays (area, tasks, accepted, err_abs, err_signed, eps_used, rounds),
+    with `converged`: False when some integral missed its tolerance within max_rounds (AQ_ENOCONV; its
+    rounds entry is negative) -- the arrays are complete either way."""
+
+    def __new__(cls, arrays, converged):
+        self = super().__new__(cls, arrays)
+        self.converged = bool(converged)
+        return self
+
+
 def _check(rc, what):
     if rc != 0:
         msg = _lib.load().aq_strerror(rc).decode()
@@ -438,6 +449,34 @@ class Context:
                                              integrand, _dp(area), _up(acc), _up(tasks), _dp(err_abs), _dp(err_signed)),
                "aq_integrate_batch_err")
         return area, tasks, acc, err_abs, err_signed
+
+    # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------
+    def integrate_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12, integrand=COSH4,
+                            theta=None, max_depth=0) -> TolResult:
+        """Every integral refined until err_abs <= max(epsabs, epsrel * |area|): rounds of error-estimate launches
+        at eps0, eps0 / shrink, ... over the integrals still missing it, tested and compacted on the device.
+        Returns TolResult(area, tasks, accepted, err_abs, err_signed, eps_used, rounds) in input order, each
+        integral's values those of the round it retired in; rounds[i] = r if it converged in round r, -r if it
+        retired there unconverged (then .converged is False; no exception). Other failures raise AquadError."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        n = a.size
+        t = self._err_theta(integrand, theta, n)
+        tol = _lib.aq_tol(float(epsabs), float(epsrel), float(eps0), float(shrink), int(max_rounds), int(max_depth))
+        area = np.empty(n, np.float64)
+        tasks = np.empty(n, np.uint64)
+        acc = np.empty(n, np.uint64)
+        err_abs = np.empty(n, np.float64)
+        err_signed = np.empty(n, np.float64)
+        eps_used = np.empty(n, np.float64)
+        rounds = np.empty(n, np.int32)
+        rc = self.L.aq_integrate_batch_tol(self._h, n, _dp(a), _dp(b), None if t is None else _dp(t), integrand,
+                                           ctypes.byref(tol), _dp(area), _up(acc), _up(tasks), _dp(err_abs),
+                                           _dp(err_signed), _dp(eps_used),
+                                           rounds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if rc != _lib.AQ_ENOCONV:
+            _check(rc, "aq_integrate_batch_tol")
+        return TolResult((area, tasks, acc, err_abs, err_signed, eps_used, rounds), rc == 0)
 
 
 class Group:

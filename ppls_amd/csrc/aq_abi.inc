@@ -165,6 +165,25 @@ struct aq_ctx {
     int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
     DevBuf<double> d_berr{&dev_bytes}; // [2][rows][2]
     PinBuf<double> h_berr;             // [n][2]
+    // tolerance-driven batch (aq_integrate_batch_tol), allocated by the first such call for its largest block
+    // so far (grow-only up to MAXK rows): the live rows' bounds, theta and original indices in two ping-pong
+    // halves (a round's survivors are compacted from one into the other), a round's gathered rows, its
+    // survivor flags and per-workgroup counts, and the block's retired records; pinned: the staging of a
+    // block's bounds and theta, its records' copy, and the survivors' count and first indices
+    DevBuf<double2> d_tbounds{&dev_bytes};   // [2][rows]
+    DevBuf<double> d_ttheta{&dev_bytes};     // [2][rows][nparams] (AQ_F_PARAM calls only)
+    DevBuf<unsigned> d_tidx{&dev_bytes};     // [2][rows]
+    DevBuf<double> d_trows{&dev_bytes};      // [rows][4] (k_gather_reset)
+    DevBuf<double> d_terr{&dev_bytes};       // [rows][2] (k_gather_err)
+    DevBuf<unsigned char> d_tflag{&dev_bytes};   // [rows]
+    DevBuf<unsigned> d_tcnt{&dev_bytes};     // [ceil(rows / TOL_T)] survivors per workgroup
+    DevBuf<double> d_ttsum{&dev_bytes};      // [ceil(rows / TOL_T)] ... and their tasks
+    DevBuf<double> d_tres{&dev_bytes};       // [rows][TOL_REC]
+    PinBuf<double2> h_tbounds;               // [rows]
+    PinBuf<double> h_ttheta;                 // [rows][nparams]
+    PinBuf<double> h_tres;                   // [rows][TOL_REC]
+    PinBuf<TolSurv> h_tsurv;                 // coherent: k_tol_compact's target
+    TolSurv* d_tsurv = nullptr;              // its device address
     // eval buffers (not counted)
     DevBuf<double> d_x, d_y;
     // host staging
@@ -696,6 +715,7 @@ const char* aq_strerror(int code) {
         case AQ_ENODEV: return "no HIP device";
         case AQ_ERCCL: return "RCCL error";
         case AQ_ERESIDENT: return "the persistent grid cannot be co-resident on the device";
+        case AQ_ENOCONV: return "an integral missed its tolerance within max_rounds";
         default: return "unknown error";
     }
 }
@@ -1683,6 +1703,188 @@ int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double*
                            double* err_signed) {
     if (!ctx || !theta_ok(integrand, theta)) return AQ_EINVAL;
     return batch_run(ctx, n, a, b, theta, eps, integrand, area, accepted, tasks, true, err_abs, err_signed);
+}
+
+// ---- tolerance-driven batch (aq_integrate_batch_tol) -----------------------------------------------------
+// The buffers of a block of `rows` integrals, on the first such call (a context that never made one holds none
+// of them: aq_ctx_device_bytes does not move until then); grow-only.
+static int tol_ensure(aq_ctx* ctx, size_t rows, bool par) {
+    constexpr size_t NP = (size_t)param::nparams;
+    AQ_HIP(ctx->d_tbounds.grow(2 * rows));
+    AQ_HIP(ctx->d_tidx.grow(2 * rows));
+    AQ_HIP(ctx->d_trows.grow(4 * rows));
+    AQ_HIP(ctx->d_terr.grow(2 * rows));
+    AQ_HIP(ctx->d_tflag.grow(rows));
+    AQ_HIP(ctx->d_tcnt.grow((rows + TOL_T - 1) / TOL_T));
+    AQ_HIP(ctx->d_ttsum.grow((rows + TOL_T - 1) / TOL_T));
+    AQ_HIP(ctx->d_tres.grow(TOL_REC * rows));
+    AQ_HIP(ctx->h_tbounds.grow(rows));
+    AQ_HIP(ctx->h_tres.grow(TOL_REC * rows));
+    if (par) {
+        AQ_HIP(ctx->d_ttheta.grow(2 * NP * rows));
+        AQ_HIP(ctx->h_ttheta.grow(NP * rows));
+    }
+    if (!ctx->h_tsurv) {
+        AQ_HIP(ctx->h_tsurv.alloc(1, true, hipHostMallocCoherent | hipHostMallocMapped));
+        AQ_HIP(hipHostGetDevicePointer((void**)&ctx->d_tsurv, ctx->h_tsurv, 0));
+    }
+    return AQ_OK;
+}
+
+// a call's outputs (any may be null)
+struct TolOut {
+    double* area;
+    uint64_t *accepted, *tasks;
+    double *err_abs, *err_signed, *eps_used;
+    int32_t* rounds;
+};
+
+// One block: m <= R integrals [a[i], b[i]] (theta rows beside them), outputs at the same offsets. R: the
+// call's rows per block, the distance of the ping-pong halves. t: defaulted. The rows' error bits are OR-ed
+// into *errbits, *noconv is set if a row retired without converging.
+static int tol_block(aq_ctx* ctx, size_t m, size_t R, const double* a, const double* b, const double* theta,
+                     int integrand, const aq_tol& t, const TolOut& o, unsigned* errbits, bool* noconv) {
+    const bool par = integrand == AQ_F_PARAM;
+    constexpr size_t NP = (size_t)param::nparams;
+    // 1. check and stage once (on the host pool), copy once into half 0, rows' indices 0 .. m-1
+    {
+        std::vector<char> ok(64, 1);
+        host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
+            for (size_t i = i0; i < i1; ++i) {
+                if (par ? !params_ok(a[i], b[i], theta + i * NP) : !bounds_ok(integrand, a[i], b[i])) {
+                    ok[p] = 0;
+                    return;
+                }
+                ctx->h_tbounds[i] = make_double2(a[i], b[i]);
+                if (par)
+                    for (size_t j = 0; j < NP; ++j) ctx->h_ttheta[i * NP + j] = theta[i * NP + j];
+            }
+        });
+        for (char c : ok)
+            if (!c) return AQ_EINVAL;
+    }
+    AQ_HIP(hipMemcpyAsync(ctx->d_tbounds, ctx->h_tbounds, sizeof(double2) * m, hipMemcpyHostToDevice, ctx->stream));
+    if (par)
+        AQ_HIP(hipMemcpyAsync(ctx->d_ttheta, ctx->h_ttheta, sizeof(double) * NP * m, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_tol_init, dim3((unsigned)((m + TOL_T - 1) / TOL_T)), dim3(TOL_T), 0, ctx->stream,
+                       ctx->d_tidx.get(), (int)m, ctx->d_hint.get());
+    AQ_HIP(hipGetLastError());
+    // the trapezoid rule's d scales as h^3, so a leaf's width as eps^(1/3): a round's trees are about
+    // shrink^(1/3) times the round before's
+    const double growth = std::cbrt(t.shrink);
+    // a launch of fewer than PCU_MAXK integrals takes its bounds from the host (kernel arguments)
+    double ha[PCU_MAXK], hb[PCU_MAXK];
+    for (size_t i = 0; i < m && i < (size_t)PCU_MAXK; ++i) ha[i] = a[i], hb[i] = b[i];
+    int k = (int)m, half = 0;
+    double eps = t.eps0;
+    for (int r = 1; k > 0; ++r, eps /= t.shrink) {
+        const bool last = r == t.max_rounds;
+        const double2* bounds = ctx->d_tbounds + (size_t)half * R;
+        const double* th = par ? ctx->d_ttheta + (size_t)half * R * NP : nullptr;
+        const unsigned* idx = ctx->d_tidx + (size_t)half * R;
+        // 2. the round: one ERR launch of the k live rows, then the batch front end's two gathers
+        LaunchArgs g;
+        g.integrand = integrand;
+        g.k = k;
+        g.a = k < PCU_MAXK ? ha : a;
+        g.b = k < PCU_MAXK ? hb : b;
+        g.eps = eps;
+        g.max_depth = t.max_depth;
+        g.dev_bounds = bounds;
+        g.dev_theta = th;
+        g.err = true;
+        g.heap = true;
+        // the job size comes from the hint the kernels before this launch preset (per-CU launches have none)
+        ctx->hint.preset = k >= PCU_MAXK;
+        int rc = launch(ctx, g);
+        ctx->hint.preset = false;
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gather_reset, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts,
+                           ctx->grid, 0, k, ctx->d_trows.get(), (const unsigned*)nullptr);
+        hipLaunchKernelGGL(k_gather_err, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, k,
+                           ctx->d_terr.get(), (const unsigned*)nullptr);
+        AQ_HIP(hipGetLastError());
+        memset(ctx->err_dirty, 0, (size_t)k);   // the gathers zeroed the slots
+        memset(ctx->dirty, 0, (size_t)k);
+        memset(ctx->parts_dirty, 0, (size_t)k);
+        // 3. test and retire; the survivors into the other half, their count to the host
+        const unsigned nb = (unsigned)((k + TOL_T - 1) / TOL_T);
+        hipLaunchKernelGGL(k_tol_test, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const double*)ctx->d_trows,
+                           (const double*)ctx->d_terr, idx, k, t.epsabs, t.epsrel, eps, r, last ? 1 : 0, ctx->d_tres.get(),
+                           ctx->d_tflag.get(), ctx->d_tcnt.get(), ctx->d_ttsum.get());
+        AQ_HIP(hipGetLastError());
+        if (last) break;   // every row retired
+        const int other = half ^ 1;
+        hipLaunchKernelGGL(k_tol_compact, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const unsigned char*)ctx->d_tflag,
+                           (const unsigned*)ctx->d_tcnt, k, bounds, th, idx, ctx->d_tbounds + (size_t)other * R,
+                           par ? ctx->d_ttheta + (size_t)other * R * NP : nullptr, ctx->d_tidx + (size_t)other * R,
+                           par ? (int)NP : 0, ctx->d_tsurv, (const double*)ctx->d_ttsum, growth, ctx->d_hint.get(),
+                           (unsigned)(ctx->grid * ERR_NW));
+        AQ_HIP(hipGetLastError());
+        // 4. the host's one look per round
+        AQ_HIP(hipStreamSynchronize(ctx->stream));
+        const unsigned left = __atomic_load_n(&ctx->h_tsurv->count, __ATOMIC_ACQUIRE);
+        if (left > (unsigned)k) return AQ_EHIP;   // (cannot happen: survivors are some of the k rows)
+        k = (int)left;
+        half = other;
+        if (k < PCU_MAXK)
+            for (int j = 0; j < k; ++j) {
+                const unsigned i = ctx->h_tsurv->idx[j];
+                if (i >= m) return AQ_EHIP;
+                ha[j] = a[i], hb[j] = b[i];
+            }
+    }
+    // 5. the block's records: one copy, unpacked on the host pool
+    AQ_HIP(hipMemcpyAsync(ctx->h_tres, ctx->d_tres, sizeof(double) * TOL_REC * m, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned> e(64, 0u);
+    std::vector<char> nc(64, 0);
+    host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
+        for (size_t i = i0; i < i1; ++i) {
+            const double* rec = ctx->h_tres + TOL_REC * i;
+            if (o.area) o.area[i] = rec[0];
+            if (o.tasks) o.tasks[i] = (uint64_t)rec[1];
+            if (o.accepted) o.accepted[i] = (uint64_t)rec[2];
+            e[p] |= (unsigned)rec[3];
+            if (o.err_abs) o.err_abs[i] = rec[4];
+            if (o.err_signed) o.err_signed[i] = rec[5];
+            if (o.eps_used) o.eps_used[i] = rec[6];
+            if (o.rounds) o.rounds[i] = (int32_t)rec[7];
+            if (rec[7] < 0.0) nc[p] = 1;
+        }
+    });
+    for (unsigned x : e) *errbits |= x;
+    for (char c : nc) *noconv |= c != 0;
+    return AQ_OK;
+}
+
+int aq_integrate_batch_tol(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, int integrand,
+                           const aq_tol* tol, double* area, uint64_t* accepted, uint64_t* tasks, double* err_abs,
+                           double* err_signed, double* eps_used, int32_t* rounds) {
+    if (!ctx || !tol || !theta_ok(integrand, theta) || (n && (!a || !b))) return AQ_EINVAL;
+    if (!tol_args_ok(*tol)) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    const aq_tol t = tol_defaulted(*tol);
+    constexpr size_t NP = (size_t)param::nparams;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const size_t R = std::min(n, (size_t)tol_block_rows(env_int("AQ_TOL_BLOCK", 0)));
+    int rc = tol_ensure(ctx, R, integrand == AQ_F_PARAM);
+    if (rc) return rc;
+    unsigned errbits = 0;
+    bool noconv = false;
+    auto at = [](auto* p, size_t off) { return p ? p + off : p; };
+    for (size_t off = 0; off < n; off += R) {
+        const TolOut o{at(area, off), at(accepted, off), at(tasks, off), at(err_abs, off), at(err_signed, off),
+                       at(eps_used, off), at(rounds, off)};
+        rc = tol_block(ctx, std::min(R, n - off), R, a + off, b + off, theta ? theta + off * NP : nullptr, integrand, t, o,
+                       &errbits, &noconv);
+        if (rc) {
+            (void)hipStreamSynchronize(ctx->stream);   // nothing of the call stays in flight
+            return rc;
+        }
+    }
+    if (errbits) return err_from_bits(errbits);
+    return noconv ? AQ_ENOCONV : AQ_OK;
 }
 
 int aq_frontier_root(aq_ctx* ctx, int integrand, double a, double b, double* d_out) {

@@ -58,4 +58,41 @@ inline std::vector<int> batch_chunks(size_t n, size_t first, size_t last) {
     return c;
 }
 
+// ---- aq_integrate_batch_tol's rules -------------------------------------------------------------------
+constexpr double TOL_DEFAULT_SHRINK = 8.0;   // err_abs of the trapezoid rule scales as eps^(2/3): a quarter per round
+constexpr int TOL_DEFAULT_ROUNDS = 12;
+constexpr int TOL_MAX_ROUNDS = 64;
+
+// the caller's aq_tol with its zeros replaced by the defaults
+inline aq_tol tol_defaulted(aq_tol t) {
+    if (t.shrink == 0.0) t.shrink = TOL_DEFAULT_SHRINK;
+    if (t.max_rounds == 0) t.max_rounds = TOL_DEFAULT_ROUNDS;
+    return t;
+}
+
+// EPSILON of round r (1-based) of a defaulted aq_tol: eps0 divided by shrink r - 1 times, one IEEE division
+// per round (not a power: a caller's loop `eps /= shrink` gives the same bits)
+inline double tol_round_eps(const aq_tol& t, int r) {
+    double e = t.eps0;
+    for (int i = 1; i < r; ++i) e /= t.shrink;
+    return e;
+}
+
+// the caller's aq_tol (zeros allowed where they mean the default); the last round's EPSILON must still be a
+// normal double (a subnormal one has lost bits of the schedule, zero would never refine less)
+inline bool tol_args_ok(const aq_tol& t0) {
+    if (!(t0.epsabs >= 0.0 && t0.epsrel >= 0.0) || t0.epsabs > 0x1.fffffffffffffp1023 || t0.epsrel > 0x1.fffffffffffffp1023)
+        return false;
+    if (t0.epsabs == 0.0 && t0.epsrel == 0.0) return false;
+    if (!(t0.eps0 > 0.0) || t0.eps0 > 0x1.fffffffffffffp1023) return false;
+    if (t0.shrink != 0.0 && !(t0.shrink >= 2.0 && t0.shrink <= 1024.0)) return false;
+    if (t0.max_rounds < 0 || t0.max_rounds > TOL_MAX_ROUNDS) return false;
+    if (t0.max_depth < 0 || t0.max_depth > AQ_MAX_LEVELS - 1) return false;
+    const aq_tol t = tol_defaulted(t0);
+    return tol_round_eps(t, t.max_rounds) >= 0x1p-1022;
+}
+
+// rows per block of an n-integral call: a whole launch, or the AQ_TOL_BLOCK override within [1, MAXK]
+inline int tol_block_rows(long long env) { return env >= 1 && env <= MAXK ? (int)env : MAXK; }
+
 }  // namespace aq

@@ -726,6 +726,142 @@ __global__ __launch_bounds__(64) void k_gather_err(double* __restrict__ err, int
     e[0] = e[1] = 0.0;
 }
 
+// ---- aq_integrate_batch_tol: between two rounds' launches -----------------------------------------------
+// A round's ERR launch of the k live rows is followed by k_gather_reset and k_gather_err (rows {area, tasks,
+// accepted, error bits} and {err_abs, err_signed} in launch order); the three kernels below read those rows
+// and know nothing of Ctl. They run in stream order, and no workgroup waits for another: k_tol_test leaves a
+// survivor flag per row and a count per workgroup, k_tol_compact sums the counts below its own workgroup.
+// The next round's launch sizes its jobs from the job-size hint (LaunchHint, as a batch chunk's launch does
+// from its pre-pass's preset): every round has another EPSILON, so the launches' own launch-to-launch hint
+// never applies. Round 1 has no figure to go by and runs one job per integral (k_tol_init); later rounds
+// take the survivors' mean tasks of the round before times `growth` (k_tol_compact).
+constexpr int TOL_T = 256;     // threads per workgroup of the two kernels (they must agree: the counts are per workgroup)
+constexpr int TOL_REC = 8;     // doubles per retired row: area, tasks, accepted, error bits, err_abs, err_signed, eps, +-round
+struct TolSurv {               // pinned host memory, written by k_tol_compact
+    unsigned count;                 // rows that survive the round
+    unsigned idx[PCU_MAXK - 1];     // the first survivors' original indices: a launch of fewer than PCU_MAXK
+};                                  // integrals takes its bounds from the host
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(TOL_T) void k_tol_init(unsigned* __restrict__ idx, int n, LaunchHint* __restrict__ hint) {
+    const int i = (int)(blockIdx.x * TOL_T + threadIdx.x);
+    if (i < n) idx[i] = (unsigned)i;
+    if (i == 0) {
+        hint->shares_next = 1u;
+        hint->per_next = 0ull;   // (unknown: the launch's fill rule adds no shares)
+    }
+}
+
+// Test and retire. Row i of the round (original index idx[i]) has converged when err_abs <= fmax(epsabs,
+// epsrel * |area|), in double, a tie included, a NaN in err_abs or area excluded. It retires -- its record
+// written at its original index -- when it converged, carries error bits, or this is the last round; the
+// record's round is negative unless it converged free of error bits.
+__global__ __launch_bounds__(TOL_T) void k_tol_test(const double* __restrict__ rows, const double* __restrict__ err,
+                                                    const unsigned* __restrict__ idx, int k, double epsabs, double epsrel,
+                                                    double eps, int round, int last, double* __restrict__ res,
+                                                    unsigned char* __restrict__ flag, unsigned* __restrict__ cnt,
+                                                    double* __restrict__ tsum) {
+    __shared__ unsigned s_wc[TOL_T / 64];
+    __shared__ double s_wt[TOL_T / 64];
+    const int i = (int)(blockIdx.x * TOL_T + threadIdx.x);
+    bool live = false;
+    double live_tasks = 0.0;   // a survivor's tasks this round (whole numbers: the sums are exact)
+    if (i < k) {
+        const double area = rows[4 * (size_t)i], tasks = rows[4 * (size_t)i + 1], acc = rows[4 * (size_t)i + 2];
+        const double bits = rows[4 * (size_t)i + 3];
+        const double ea = err[2 * (size_t)i], es = err[2 * (size_t)i + 1];
+        const bool conv = !(ea != ea) && !(area != area) && ea <= fmax(epsabs, epsrel * fabs(area));
+        const bool clean = bits == 0.0;
+        live = !(conv || !clean || last);
+        if (!live) {
+            double* o = res + TOL_REC * (size_t)idx[i];
+            o[0] = area; o[1] = tasks; o[2] = acc; o[3] = bits;
+            o[4] = ea; o[5] = es; o[6] = eps;
+            o[7] = conv && clean ? (double)round : -(double)round;
+        }
+        flag[i] = live ? 1 : 0;
+        if (live) live_tasks = tasks;
+    }
+    const unsigned long long m = __ballot(live);
+    const double wt = wave_sum_f64(live_tasks);
+    if (lane_id() == 0) {
+        s_wc[threadIdx.x >> 6] = (unsigned)__popcll(m);
+        s_wt[threadIdx.x >> 6] = wt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned c = 0;
+        double t = 0.0;
+        for (int v = 0; v < TOL_T / 64; ++v) c += s_wc[v], t += s_wt[v];
+        cnt[blockIdx.x] = c;
+        tsum[blockIdx.x] = t;
+    }
+}
+
+// Stable compaction of the survivors' {a, b}, theta rows (np doubles each; none when np == 0) and original
+// indices into the other ping-pong buffers, in input order: a row's place is the survivors of the workgroups
+// below (cnt) + of the waves below in its workgroup + of the lanes below in its wave (ballot / mbcnt). The
+// count and the first survivors' indices go to pinned host memory. The last workgroup, which sums every count,
+// also sums the survivors' tasks (tsum) and presets the next launch's job size from their mean times `growth`
+// (k_batch_scatter's rule: about TASKS_PER_JOB tasks per job, at most max_shares shares per integral).
+__global__ __launch_bounds__(TOL_T) void k_tol_compact(const unsigned char* __restrict__ flag, const unsigned* __restrict__ cnt,
+                                                       int k, const double2* __restrict__ b_in,
+                                                       const double* __restrict__ th_in, const unsigned* __restrict__ i_in,
+                                                       double2* __restrict__ b_out, double* __restrict__ th_out,
+                                                       unsigned* __restrict__ i_out, int np, TolSurv* __restrict__ host,
+                                                       const double* __restrict__ tsum, double growth,
+                                                       LaunchHint* __restrict__ hint, unsigned max_shares) {
+    __shared__ unsigned s_base[TOL_T / 64], s_wc[TOL_T / 64];
+    __shared__ double s_wt[TOL_T / 64];
+    const bool last_wg = blockIdx.x == gridDim.x - 1;
+    unsigned part = 0;
+    for (unsigned j = threadIdx.x; j < blockIdx.x; j += TOL_T) part += cnt[j];
+    part = wave_sum_u(part);
+    double tpart = 0.0;
+    if (last_wg)
+        for (unsigned j = threadIdx.x; j < gridDim.x; j += TOL_T) tpart += tsum[j];
+    tpart = wave_sum_f64(tpart);
+    const int i = (int)(blockIdx.x * TOL_T + threadIdx.x);
+    const bool live = i < k && flag[i] != 0;
+    const unsigned long long m = __ballot(live);
+    const unsigned w = threadIdx.x >> 6;
+    if (lane_id() == 0) {
+        s_base[w] = part;
+        s_wc[w] = (unsigned)__popcll(m);
+        s_wt[w] = tpart;
+    }
+    __syncthreads();
+    unsigned off = 0, mine = 0;
+    for (unsigned v = 0; v < (unsigned)(TOL_T / 64); ++v) {
+        off += s_base[v] + (v < w ? s_wc[v] : 0u);
+        mine += s_base[v] + s_wc[v];
+    }
+    if (live) {
+        const unsigned pos = off + mbcnt(m);   // < k: at most the rows before this one survive
+        const unsigned orig = i_in[i];
+        b_out[pos] = b_in[i];
+        i_out[pos] = orig;
+        for (int j = 0; j < np; ++j) th_out[(size_t)pos * np + j] = th_in[(size_t)i * np + j];
+        if (pos < (unsigned)(PCU_MAXK - 1)) host->idx[pos] = orig;
+    }
+    if (last_wg && threadIdx.x == 0) {
+        host->count = mine;
+        if (mine) {
+            double t = 0.0;
+            for (int v = 0; v < TOL_T / 64; ++v) t += s_wt[v];
+            const double per = growth * t / (double)mine;   // predicted tasks per surviving integral
+            const double sh = floor((per + 0.5 * TASKS_PER_JOB) / TASKS_PER_JOB);
+            hint->shares_next = (unsigned)fmin(fmax(sh, 1.0), (double)max_shares);
+            hint->per_next = (unsigned long long)fmax(per, 0.0);
+        }
+    }
+}
+
 // The same slots as exact int64 rows (AQ_EXACT_ROW each): limbs, tasks, accepted, spilled,
 // levels | error << 32. Sums of such rows (an int64 all-reduce) keep the area exact.
 __global__ __launch_bounds__(64) void k_gather_exact(const Ctl* __restrict__ ctls,

@@ -2,7 +2,7 @@
  * aquad_cli.c -- drop-in for `mpirun -n P ./aquadPartA` (/root/reference/aquadPartA.c main(), :78-123).
  *
  *   aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] [--theta v0,v1,...]
- *         [--per-cu] [--levels] [--err]
+ *         [--per-cu] [--levels] [--err] [--epsrel R] [--epsabs A] [--eps0 E0] [--shrink S]
  *
  * Same observable surface as the reference: `Area=%lf`, a blank line, `Tasks Per Process`, the index
  * row and the count row (tab-terminated entries). Process 0 is the farmer and always reports 0 tasks
@@ -17,6 +17,10 @@
  * `--err` (one GPU, no --levels) runs the error-estimate form (aq_integrate_err): the printout is unchanged,
  * and two lines follow it, `Error estimate=%.6e` (the sum of |d| over the accepted intervals, d the
  * difference the test at :191 bounds) and `Extrapolated area=%.17g` (aq_err_extrapolate).
+ * `--epsrel R` and / or `--epsabs A` (one GPU, no --levels, one worker column, no --per-cu) refine the integral
+ * until its error estimate is at most max(A, R * |area|) (aq_integrate_batch_tol on the one integral: rounds at
+ * EPSILON E0, E0 / S, ...; --eps0 defaults to --eps, --shrink to 8): the printout of the round it retired in,
+ * the two --err lines, and `Rounds=<r> eps=<EPSILON of that round, %.17g>` (r negative: not converged, exit 3).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -28,7 +32,7 @@
 static void usage(void) {
     fprintf(stderr,
             "usage: aquad [-n P] [--gpus G] [--eps E] [--a A] [--b B] [--f cosh4|sin_recip|user|param] "
-            "[--theta v0,v1,...] [--per-cu] [--levels] [--err]\n");
+            "[--theta v0,v1,...] [--per-cu] [--levels] [--err] [--epsrel R] [--epsabs A] [--eps0 E0] [--shrink S]\n");
 }
 
 int main(int argc, char **argv) {
@@ -37,6 +41,9 @@ int main(int argc, char **argv) {
     aq_err err = {0.0, 0.0};
     double theta[AQ_MAX_PARAMS] = {0};
     int ntheta = 0;
+    aq_tol tol = {0.0, 0.0, 0.0, 0.0, 0, 0};
+    int with_tol = 0, rounds = 0;
+    double eps_used = 0.0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -66,6 +73,10 @@ int main(int argc, char **argv) {
         } else if (!strcmp(a, "--per-cu")) per_cu = 1;
         else if (!strcmp(a, "--levels")) levels = 1;
         else if (!strcmp(a, "--err")) with_err = 1;
+        else if (!strcmp(a, "--epsrel") && v) { tol.epsrel = atof(v); with_tol = 1; ++i; }
+        else if (!strcmp(a, "--epsabs") && v) { tol.epsabs = atof(v); with_tol = 1; ++i; }
+        else if (!strcmp(a, "--eps0") && v) { tol.eps0 = atof(v); ++i; }
+        else if (!strcmp(a, "--shrink") && v) { tol.shrink = atof(v); ++i; }
         else { usage(); return 2; }
     }
     if (p.integrand == AQ_F_PARAM ? (ntheta != aq_param_count() || gpus != 1) : ntheta != 0) {
@@ -75,6 +86,10 @@ int main(int argc, char **argv) {
     }
     if (with_err && (gpus != 1 || levels)) {
         fprintf(stderr, "aquad: --err runs on one GPU and keeps no level histograms\n");
+        return 2;
+    }
+    if (with_tol && (gpus != 1 || levels || per_cu || (nprocs != -1 && nprocs != 2))) {
+        fprintf(stderr, "aquad: --epsrel / --epsabs run on one GPU with one worker column and keep no level histograms\n");
         return 2;
     }
     if (nprocs == -1) nprocs = 1 + gpus;
@@ -99,7 +114,18 @@ int main(int argc, char **argv) {
     res.tasks_per_gpu = per_gpu;
     res.tasks_per_cu = cu;
     if (rc == AQ_OK) {
-        if (with_err) {
+        if (with_tol) {
+            if (tol.eps0 == 0.0) tol.eps0 = p.eps;
+            tol.max_depth = p.max_depth;
+            uint64_t accepted = 0;
+            rc = aq_integrate_batch_tol(ctx[0], 1, &p.a, &p.b, p.integrand == AQ_F_PARAM ? theta : NULL, p.integrand, &tol,
+                                        &res.area, &accepted, &res.tasks, &err.err_abs, &err.err_signed, &eps_used,
+                                        &rounds);
+            res.accepted = accepted;
+            res.n_gpus = 1;
+            per_gpu[0] = res.tasks;
+            if (rc == AQ_ENOCONV) rc = AQ_OK;   /* reported by the sign of Rounds= and the exit code */
+        } else if (with_err) {
             rc = aq_integrate_err(ctx[0], &p, p.integrand == AQ_F_PARAM ? theta : NULL, &res, &err);
         } else if (gpus == 1) {
             rc = p.integrand == AQ_F_PARAM ? aq_integrate_params(ctx[0], &p, theta, &res) : aq_integrate(ctx[0], &p, &res);
@@ -126,10 +152,11 @@ int main(int argc, char **argv) {
         aq_print_reference_procs(stdout, res.area, tpp, cols + 1);
         free(tpp);
     }
-    if (with_err) {
+    if (with_err || with_tol) {
         fprintf(stdout, "Error estimate=%.6e\n", err.err_abs);
         fprintf(stdout, "Extrapolated area=%.17g\n", aq_err_extrapolate(res.area, &err));
     }
+    if (with_tol) fprintf(stdout, "Rounds=%d eps=%.17g\n", rounds, eps_used);
     if (levels) {
         uint64_t t[AQ_MAX_LEVELS], l[AQ_MAX_LEVELS];
         aq_level_histogram(ctx[0], t, l, AQ_MAX_LEVELS);
@@ -143,5 +170,6 @@ int main(int argc, char **argv) {
     free(cu);
     free(per_gpu);
     free(ctx);
+    if (with_tol && rounds < 0) return 3;
     return 0;
 }
