@@ -125,6 +125,24 @@ def _theta(theta, n):
     return t
 
 
+def _batch_arrays(a, b, out=None, theta=lambda n: None):
+    """The batch calls' common front: (a, b, n, theta(n), area, tasks, acc) -- the bounds as contiguous f64, the
+    call's theta rows checked for n integrals, and the three result arrays: fresh, or the caller's `out` checked.
+    (theta is a callable so that its check runs between the bounds' and `out`'s: the order in which a call with
+    several bad arguments has always raised.)"""
+    a = np.ascontiguousarray(a, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    n = a.size
+    t = theta(n)
+    if out is None:
+        return a, b, n, t, np.empty(n, np.float64), np.empty(n, np.uint64), np.empty(n, np.uint64)
+    area, tasks, acc = out
+    for x, dt in ((area, np.float64), (tasks, np.uint64), (acc, np.uint64)):
+        if x.dtype != dt or x.shape != (n,) or not x.flags.c_contiguous or not x.flags.writeable:
+            raise ValueError("out arrays must be writeable contiguous (f64, u64, u64) of the batch's size")
+    return a, b, n, t, area, tasks, acc
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     _lib.load().aq_device_count(ctypes.byref(n))
@@ -317,18 +335,7 @@ class Context:
         """(area, tasks, accepted) per integral. out: optional (area f64, tasks u64, accepted u64)
         contiguous arrays of n to write into (a caller that reuses them skips the first-touch page
         faults of three fresh arrays)."""
-        a = np.ascontiguousarray(a, np.float64)
-        b = np.ascontiguousarray(b, np.float64)
-        n = a.size
-        if out is None:
-            area = np.empty(n, np.float64)
-            tasks = np.empty(n, np.uint64)
-            acc = np.empty(n, np.uint64)
-        else:
-            area, tasks, acc = out
-            for x, dt in ((area, np.float64), (tasks, np.uint64), (acc, np.uint64)):
-                if x.dtype != dt or x.shape != (n,) or not x.flags.c_contiguous or not x.flags.writeable:
-                    raise ValueError("out arrays must be writeable contiguous (f64, u64, u64) of the batch's size")
+        a, b, n, _, area, tasks, acc = _batch_arrays(a, b, out)
         _check(self.L.aq_integrate_batch(self._h, n, _dp(a), _dp(b), float(eps), integrand, _dp(area), _up(acc),
                                          _up(tasks)), "aq_integrate_batch")
         return area, tasks, acc
@@ -372,19 +379,7 @@ class Context:
 
     def integrate_batch_params(self, a, b, theta, eps, out=None):
         """integrate_batch for the family: (area, tasks, accepted) per integral, in input order."""
-        a = np.ascontiguousarray(a, np.float64)
-        b = np.ascontiguousarray(b, np.float64)
-        n = a.size
-        t = _theta(theta, n)
-        if out is None:
-            area = np.empty(n, np.float64)
-            tasks = np.empty(n, np.uint64)
-            acc = np.empty(n, np.uint64)
-        else:
-            area, tasks, acc = out
-            for x, dt in ((area, np.float64), (tasks, np.uint64), (acc, np.uint64)):
-                if x.dtype != dt or x.shape != (n,) or not x.flags.c_contiguous or not x.flags.writeable:
-                    raise ValueError("out arrays must be writeable contiguous (f64, u64, u64) of the batch's size")
+        a, b, n, t, area, tasks, acc = _batch_arrays(a, b, out, lambda n: _theta(theta, n))
         _check(self.L.aq_integrate_batch_params(self._h, n, _dp(a), _dp(b), _dp(t), float(eps), _dp(area), _up(acc),
                                                 _up(tasks)), "aq_integrate_batch_params")
         return area, tasks, acc
@@ -436,13 +431,7 @@ class Context:
     def integrate_batch_err(self, a, b, eps, integrand=COSH4, theta=None):
         """integrate_batch (or, with theta, integrate_batch_params) with the error estimate: (area, tasks, accepted,
         err_abs, err_signed) per integral, in input order."""
-        a = np.ascontiguousarray(a, np.float64)
-        b = np.ascontiguousarray(b, np.float64)
-        n = a.size
-        t = self._err_theta(integrand, theta, n)
-        area = np.empty(n, np.float64)
-        tasks = np.empty(n, np.uint64)
-        acc = np.empty(n, np.uint64)
+        a, b, n, t, area, tasks, acc = _batch_arrays(a, b, None, lambda n: self._err_theta(integrand, theta, n))
         err_abs = np.empty(n, np.float64)
         err_signed = np.empty(n, np.float64)
         _check(self.L.aq_integrate_batch_err(self._h, n, _dp(a), _dp(b), None if t is None else _dp(t), float(eps),
@@ -458,14 +447,8 @@ class Context:
         Returns TolResult(area, tasks, accepted, err_abs, err_signed, eps_used, rounds) in input order, each
         integral's values those of the round it retired in; rounds[i] = r if it converged in round r, -r if it
         retired there unconverged (then .converged is False; no exception). Other failures raise AquadError."""
-        a = np.ascontiguousarray(a, np.float64)
-        b = np.ascontiguousarray(b, np.float64)
-        n = a.size
-        t = self._err_theta(integrand, theta, n)
+        a, b, n, t, area, tasks, acc = _batch_arrays(a, b, None, lambda n: self._err_theta(integrand, theta, n))
         tol = _lib.aq_tol(float(epsabs), float(epsrel), float(eps0), float(shrink), int(max_rounds), int(max_depth))
-        area = np.empty(n, np.float64)
-        tasks = np.empty(n, np.uint64)
-        acc = np.empty(n, np.uint64)
         err_abs = np.empty(n, np.float64)
         err_signed = np.empty(n, np.float64)
         eps_used = np.empty(n, np.float64)

@@ -2,6 +2,7 @@
 // Host side: the C ABI of include/aquad.h (included by aquad.hip after the kernels).
 // ================================================================================================
 #include "aq_host_args.h"   // the argument rules and the chunk schedule (no HIP: tests/test_host_args.py)
+#include "aq_batch_plan.h"  // the batch front end's pipeline: steps, streams, events (no HIP: tests/test_batch_plan.py)
 #include "aq_host_mem.h"    // owning device / pinned buffers, events, streams
 
 using namespace aq;
@@ -81,6 +82,123 @@ struct HostOut {
     unsigned long long cu[AQ_CU_SLOTS] = {};
 };
 
+// The batch front end's buffers (aq_integrate_batch, _params, _err). The device keeps rings of two chunks,
+// indexed by chunk parity and `R` rows apart -- bounds, rows {area, tasks, accepted, error}, theta, error sums,
+// size order and its permutation -- and one chunk's size keys, for the largest chunk so far (grow-only up to
+// MAXK rows, whatever n: ADVICE r5 -- they had been sized to the whole batch, 72 B per integral); the pinned
+// host copies cover the whole call (grow-only). Who may touch which parity when: aq_batch_plan.h.
+struct BatchRings {
+    DevBuf<double> rows;        // [2][R][4]
+    DevBuf<double2> bounds;     // [2][R]
+    DevBuf<double2> sorted;     // [2][R] the chunk's bounds in size order (k_batch_scatter)
+    DevBuf<unsigned> key;       // [R] size class per integral (k_batch_estimate)
+    DevBuf<unsigned> perm;      // [2][R] sorted position -> integral
+    DevBuf<unsigned> cnt;       // [2] x (EST_KEYS counts + EST_KEYS cursors)
+    DevBuf<double> est;         // [2] the chunk's sum of size estimates
+    DevBuf<double> theta;       // [2][R][nparams] (the first aq_integrate_batch_params)
+    DevBuf<double> thsorted;    // [2][R][nparams] (k_batch_scatter_theta)
+    DevBuf<double> errrows;     // [2][R][2] {err_abs, err_signed} (the first aq_integrate_batch_err)
+    PinBuf<double> h_rows;      // [n][4]
+    PinBuf<double2> h_bounds;   // [n]
+    PinBuf<double> h_theta;     // [n][nparams]
+    PinBuf<double> h_errrows;   // [n][2]
+    size_t R = 0;               // the current call's largest chunk (every ring holds at least two of it)
+    bool par = false, err = false;   // ... and whether theta rows / error rows travel in it
+    explicit BatchRings(unsigned long long* bytes)
+        : rows{bytes}, bounds{bytes}, sorted{bytes}, key{bytes}, perm{bytes}, cnt{bytes}, est{bytes}, theta{bytes},
+          thsorted{bytes}, errrows{bytes} {}
+
+    // for a call of n integrals in chunks of at most `chunk_rows`, with theta rows (par_) and error rows (err_)
+    int grow(size_t chunk_rows, size_t n, bool par_, bool err_) {
+        constexpr size_t NP = (size_t)param::nparams;
+        R = chunk_rows, par = par_, err = err_;
+        AQ_HIP(rows.grow(8 * R));
+        AQ_HIP(bounds.grow(2 * R));
+        AQ_HIP(sorted.grow(2 * R));
+        AQ_HIP(key.grow(R));
+        AQ_HIP(perm.grow(2 * R));
+        AQ_HIP(cnt.grow(4 * EST_KEYS));
+        AQ_HIP(est.grow(2));
+        AQ_HIP(h_rows.grow(4 * n));
+        AQ_HIP(h_bounds.grow(n));
+        if (par) {
+            AQ_HIP(theta.grow(NP * 2 * R));
+            AQ_HIP(thsorted.grow(NP * 2 * R));
+            AQ_HIP(h_theta.grow(NP * n));
+        }
+        if (err) {
+            AQ_HIP(errrows.grow(4 * R));
+            AQ_HIP(h_errrows.grow(2 * n));
+        }
+        return AQ_OK;
+    }
+
+    // chunk c's places in the rings (null where the call has none: theta, error rows)
+    struct View {
+        double* rows;
+        double2 *bounds, *sorted;
+        unsigned *perm, *cnt, *cnt_next;   // (cnt_next, est_next: the other parity's, which the scatter zeroes)
+        double *est, *est_next, *theta, *thsorted, *errrows;
+    };
+    View at(size_t c) const {
+        constexpr size_t NP = (size_t)param::nparams;
+        const size_t p = c & 1u;
+        return View{rows + 4 * p * R, bounds + p * R, sorted + p * R, perm + p * R, cnt + 2 * EST_KEYS * p,
+                    cnt + 2 * EST_KEYS * (p ^ 1u), est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr,
+                    par ? thsorted + p * R * NP : nullptr, err ? errrows + 2 * p * R : nullptr};
+    }
+};
+
+// aq_integrate_batch_tol's buffers, for its largest block so far (grow-only up to MAXK rows): the live rows'
+// bounds, theta and original indices in two ping-pong halves (a round's survivors are compacted from one into
+// the other), a round's gathered rows, its survivor flags and per-workgroup counts, and the block's retired
+// records; pinned: the staging of a block's bounds and theta, its records' copy, and the survivors' count and
+// first indices.
+struct TolBufs {
+    DevBuf<double2> bounds;      // [2][rows]
+    DevBuf<double> theta;        // [2][rows][nparams] (AQ_F_PARAM calls only)
+    DevBuf<unsigned> idx;        // [2][rows]
+    DevBuf<double> rows;         // [rows][4] (k_gather_reset)
+    DevBuf<double> err;          // [rows][2] (k_gather_err)
+    DevBuf<unsigned char> flag;  // [rows]
+    DevBuf<unsigned> cnt;        // [ceil(rows / TOL_T)] survivors per workgroup
+    DevBuf<double> tsum;         // [ceil(rows / TOL_T)] ... and their tasks
+    DevBuf<double> res;          // [rows][TOL_REC]
+    PinBuf<double2> h_bounds;    // [rows]
+    PinBuf<double> h_theta;      // [rows][nparams]
+    PinBuf<double> h_res;        // [rows][TOL_REC]
+    PinBuf<TolSurv> h_surv;      // coherent: k_tol_compact's target
+    TolSurv* d_surv = nullptr;   // its device address
+    explicit TolBufs(unsigned long long* bytes)
+        : bounds{bytes}, theta{bytes}, idx{bytes}, rows{bytes}, err{bytes}, flag{bytes}, cnt{bytes}, tsum{bytes},
+          res{bytes} {}
+
+    // for blocks of `n` rows, on the first such call (a context that never made one holds none of these:
+    // aq_ctx_device_bytes does not move until then)
+    int ensure(size_t n, bool par) {
+        constexpr size_t NP = (size_t)param::nparams;
+        AQ_HIP(bounds.grow(2 * n));
+        AQ_HIP(idx.grow(2 * n));
+        AQ_HIP(rows.grow(4 * n));
+        AQ_HIP(err.grow(2 * n));
+        AQ_HIP(flag.grow(n));
+        AQ_HIP(cnt.grow((n + TOL_T - 1) / TOL_T));
+        AQ_HIP(tsum.grow((n + TOL_T - 1) / TOL_T));
+        AQ_HIP(res.grow(TOL_REC * n));
+        AQ_HIP(h_bounds.grow(n));
+        AQ_HIP(h_res.grow(TOL_REC * n));
+        if (par) {
+            AQ_HIP(theta.grow(2 * NP * n));
+            AQ_HIP(h_theta.grow(NP * n));
+        }
+        if (!h_surv) {
+            AQ_HIP(h_surv.alloc(1, true, hipHostMallocCoherent | hipHostMallocMapped));
+            AQ_HIP(hipHostGetDevicePointer((void**)&d_surv, h_surv, 0));
+        }
+        return AQ_OK;
+    }
+};
+
 }  // namespace
 
 struct aq_ctx {
@@ -132,58 +250,18 @@ struct aq_ctx {
     bool defer_fold = false;           // aq_level_defer_fold: level steps leave their rows for one later fold
     int lp_pending = 0;                // level-step rows written and not yet folded
     double* lp_acc = nullptr;          // ... into this accumulator (the caller's)
-    // batch front end: rows {area, tasks, accepted, error} and bounds. The device keeps two chunks' bounds
-    // and two chunks' rows (rings indexed by chunk parity: at most chunk c + 1's bounds and chunks c, c - 1's
-    // rows are in flight) and one chunk's size-order buffers, for the largest chunk so far (grow-only up to
-    // MAXK rows, whatever n: ADVICE r5 -- they had been sized to the whole batch, 72 B per integral); the
-    // pinned host copies cover the whole call (grow-only)
-    DevBuf<double> d_batch{&dev_bytes};      // [2][rows][4]
-    PinBuf<double> h_batch;                  // [n][4]
-    DevBuf<double2> d_bbounds{&dev_bytes};   // [2][rows]
-    PinBuf<double2> h_bbounds;               // [n]
-    DevBuf<double2> d_bsorted{&dev_bytes};   // the chunk's bounds in size order (k_batch_scatter; 2 parities)
-    DevBuf<unsigned> d_bkey{&dev_bytes};     // size class per integral (k_batch_estimate)
-    DevBuf<unsigned> d_bperm{&dev_bytes};    // sorted position -> integral (2 parities)
-    DevBuf<unsigned> d_bcnt{&dev_bytes};     // EST_KEYS counts + EST_KEYS cursors
-    DevBuf<double> d_best{&dev_bytes};       // the chunk's sum of size estimates (per chunk parity)
-    // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params; the
-    // batch rings by the first aq_integrate_batch_params): NSLOTS + 1 rows on the device beside d_bounds,
-    // their pinned staging ring, and the batch front end's rows -- two chunks' theta and two chunks' theta
-    // in size order, sized like d_bbounds / d_bsorted, and the pinned copy of the whole call
+    BatchRings batch{&dev_bytes};      // the batch front end's rings and pinned copies (grown by its calls)
+    // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
+    // rows on the device beside d_bounds, and their pinned staging ring
     DevBuf<double> d_theta{&dev_bytes};      // [NSLOTS_ALL][nparams]
     PinBuf<double> h_theta;                  // pinned staging ring, NSTAGE x NSLOTS x nparams
-    DevBuf<double> d_btheta{&dev_bytes};     // [2][rows][nparams]
-    DevBuf<double> d_bthsorted{&dev_bytes};  // [2][rows][nparams] (k_batch_scatter_theta)
-    PinBuf<double> h_btheta;                 // [n][nparams]
-    // error estimate (the ERR launches, aq_*_err), allocated by the first ERR call (ensure_err; the batch
-    // rings by the first aq_integrate_batch_err): the slots' two sums, and the batch front end's rows -- two
-    // chunks' {err_abs, err_signed} on the device and the pinned copy of the whole call
+    // error estimate (the ERR launches, aq_*_err), allocated by the first ERR call (ensure_err): the slots' two sums
     DevBuf<double> d_err{&dev_bytes};  // [NSLOTS_ALL][2] = Σ|d|, Σd over the slot's accepted tasks
     PinBuf<double> h_err;              // one pair (aq_fetch_err)
     bool err_dirty[NSLOTS_ALL] = {};   // slot's pair written since it was last zeroed
     bool slot_err[NSLOTS_ALL] = {};    // slot's last launch was an ERR launch (beside slot_hist)
     int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
-    DevBuf<double> d_berr{&dev_bytes}; // [2][rows][2]
-    PinBuf<double> h_berr;             // [n][2]
-    // tolerance-driven batch (aq_integrate_batch_tol), allocated by the first such call for its largest block
-    // so far (grow-only up to MAXK rows): the live rows' bounds, theta and original indices in two ping-pong
-    // halves (a round's survivors are compacted from one into the other), a round's gathered rows, its
-    // survivor flags and per-workgroup counts, and the block's retired records; pinned: the staging of a
-    // block's bounds and theta, its records' copy, and the survivors' count and first indices
-    DevBuf<double2> d_tbounds{&dev_bytes};   // [2][rows]
-    DevBuf<double> d_ttheta{&dev_bytes};     // [2][rows][nparams] (AQ_F_PARAM calls only)
-    DevBuf<unsigned> d_tidx{&dev_bytes};     // [2][rows]
-    DevBuf<double> d_trows{&dev_bytes};      // [rows][4] (k_gather_reset)
-    DevBuf<double> d_terr{&dev_bytes};       // [rows][2] (k_gather_err)
-    DevBuf<unsigned char> d_tflag{&dev_bytes};   // [rows]
-    DevBuf<unsigned> d_tcnt{&dev_bytes};     // [ceil(rows / TOL_T)] survivors per workgroup
-    DevBuf<double> d_ttsum{&dev_bytes};      // [ceil(rows / TOL_T)] ... and their tasks
-    DevBuf<double> d_tres{&dev_bytes};       // [rows][TOL_REC]
-    PinBuf<double2> h_tbounds;               // [rows]
-    PinBuf<double> h_ttheta;                 // [rows][nparams]
-    PinBuf<double> h_tres;                   // [rows][TOL_REC]
-    PinBuf<TolSurv> h_tsurv;                 // coherent: k_tol_compact's target
-    TolSurv* d_tsurv = nullptr;              // its device address
+    TolBufs tol{&dev_bytes};           // aq_integrate_batch_tol's buffers (allocated by its first call)
     // eval buffers (not counted)
     DevBuf<double> d_x, d_y;
     // host staging
@@ -1396,33 +1474,195 @@ static void host_parallel(aq_ctx* ctx, size_t n, size_t grain, F&& f) {
     ctx->pool->run(parts, piece);
 }
 
-// theta: the parametrised family's rows [n][nparams] (integrand AQ_F_PARAM, aq_integrate_batch_params), else
-// null. The rows travel with the bounds: checked and staged with them, copied by the same stream into
-// their own device ring, carried into size order behind k_batch_scatter (k_batch_scatter_theta).
-// err: the ERR form (aq_integrate_batch_err) -- every chunk is an ERR launch, and its slots' error sums follow
-// the rows: gathered behind them in the same order (k_gather_err), copied back by the same stream, unpacked
-// with them into err_abs / err_signed (either may be null).
+// ---- steps the batch front end and the tolerance loop share ----------------------------------------------
+// Check m integrals [a[i], b[i]] (AQ_F_PARAM: with their theta rows) and stage them in the pinned hb (and ht),
+// on the host pool. AQ_EINVAL on a bad row.
+static int check_and_stage(aq_ctx* ctx, int integrand, size_t m, const double* a, const double* b, const double* theta,
+                           double2* hb, double* ht) {
+    const bool par = integrand == AQ_F_PARAM;
+    constexpr size_t NP = (size_t)param::nparams;
+    std::vector<char> ok(64, 1);
+    host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
+        for (size_t i = i0; i < i1; ++i) {
+            if (par ? !params_ok(a[i], b[i], theta + i * NP) : !bounds_ok(integrand, a[i], b[i])) {
+                ok[p] = 0;
+                return;
+            }
+            hb[i] = make_double2(a[i], b[i]);
+            if (par)
+                for (size_t j = 0; j < NP; ++j) ht[i * NP + j] = theta[i * NP + j];
+        }
+    });
+    for (char o : ok)
+        if (!o) return AQ_EINVAL;
+    return AQ_OK;
+}
+
+// Behind a launch into slots 0 .. k-1, on the context's stream: slot s's row {area, tasks, accepted, error} to
+// rows[perm ? perm[s] : s] (k_gather_reset) and, behind an ERR launch, its error sums to errrows likewise
+// (k_gather_err; null: not an ERR launch). The kernels return the slots to zero: no k_reset before the next
+// launch, and the slots count as clean.
+static int gather_clean(aq_ctx* ctx, int k, double* rows, double* errrows, const unsigned* perm) {
+    hipLaunchKernelGGL(k_gather_reset, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts, ctx->grid, 0,
+                       k, rows, perm);
+    if (errrows)
+        hipLaunchKernelGGL(k_gather_err, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, k, errrows, perm);
+    AQ_HIP(hipGetLastError());
+    if (errrows) memset(ctx->err_dirty, 0, (size_t)k);
+    memset(ctx->dirty, 0, (size_t)k);
+    memset(ctx->parts_dirty, 0, (size_t)k);
+    return AQ_OK;
+}
+
+// a call's per-integral outputs (any may be null)
+struct RowsOut {
+    double* area;
+    uint64_t *accepted, *tasks;
+    double *err_abs, *err_signed;
+    RowsOut from(size_t i) const {
+        auto at = [i](auto* p) { return p ? p + i : p; };
+        return RowsOut{at(area), at(accepted), at(tasks), at(err_abs), at(err_signed)};
+    }
+};
+
+// m pinned rows {area, tasks, accepted, error bits, ...}, `stride` doubles apart, into o[0 .. m), and their
+// {err_abs, err_signed} pairs, `estride` apart at errs, into o's error outputs; on the host pool. extra(i, row,
+// piece) sees every row as well (a layout's further fields). Returns the OR of the rows' error bits.
+extern "C++" template <typename Extra>
+static unsigned unpack_rows(aq_ctx* ctx, size_t m, const double* rows, size_t stride, const double* errs, size_t estride,
+                            const RowsOut& o, Extra&& extra) {
+    std::vector<unsigned> e(64, 0u);
+    host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
+        unsigned bits = 0;
+        for (size_t i = i0; i < i1; ++i) {
+            const double* row = rows + stride * i;
+            if (o.area) o.area[i] = row[0];
+            if (o.tasks) o.tasks[i] = (uint64_t)row[1];
+            if (o.accepted) o.accepted[i] = (uint64_t)row[2];
+            bits |= (unsigned)row[3];
+            if (o.err_abs) o.err_abs[i] = errs[estride * i];
+            if (o.err_signed) o.err_signed[i] = errs[estride * i + 1];
+            extra(i, row, p);
+        }
+        e[p] = bits;
+    });
+    unsigned bits = 0;
+    for (unsigned x : e) bits |= x;
+    return bits;
+}
+
+// ---- the batch front end (SURVEY config 3) ----------------------------------------------------------------
+// Up to MAXK integrals per persistent launch, every integral with its own slot, n integrals as chunks
+// (batch_chunks): a small first chunk starts the device early, a small last one shortens the copy-back after
+// it. Four streams (r05, r06; profiles/r05a/c3_timeline_r04code.json had the launches wait ~0.5 ms per chunk
+// for a reset, a bounds copy, a full-width gather and a rows copy): the host checks and stages chunk c + 1
+// while chunk c runs, s_h2d copies it into its own device rows, s_pre puts it into size order (largest trees
+// first: the launch's tail is its smallest jobs; AQ_BATCH_SORT=0: off) as chunk c's launch frees the CUs, the
+// context's stream runs the launches and gathers, s_d2h copies chunk c's rows back while chunk c + 1 runs and
+// the host unpacks chunk c - 1. Which step runs where, behind what: batch_plan (aq_batch_plan.h). BatchCall
+// is one call's state and one function per step kind -- it orders nothing.
+//
+// theta: the parametrised family's rows [n][nparams] (integrand AQ_F_PARAM), else null; they travel with the
+// bounds. The ERR form's (plan.err) slots' error sums travel with the rows.
+struct BatchCall {
+    aq_ctx* ctx;
+    const BatchRings& B;       // ctx->batch
+    const BatchPlan& plan;
+    std::vector<size_t> off;   // chunk c: integrals [off[c], off[c + 1])
+    const double *a, *b, *theta;
+    double eps;
+    int integrand;
+    RowsOut out;
+    unsigned errbits = 0;
+    static constexpr size_t NP = (size_t)param::nparams;
+
+    int zero(hipStream_t s) {
+        AQ_HIP(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4 * EST_KEYS, s));
+        AQ_HIP(hipMemsetAsync(B.est, 0, sizeof(double) * 2, s));
+        return AQ_OK;
+    }
+    // (on several host threads: the first chunk's is the only host work before the device starts, the next
+    // ones' must stay shorter than a launch)
+    int stage(int c) {
+        return check_and_stage(ctx, integrand, (size_t)plan.chunks[c], a + off[c], b + off[c],
+                               plan.theta ? theta + off[c] * NP : nullptr, B.h_bounds + off[c],
+                               plan.theta ? B.h_theta + off[c] * NP : nullptr);
+    }
+    int h2d(int c, hipStream_t s) {
+        const BatchRings::View v = B.at(c);
+        const size_t m = (size_t)plan.chunks[c];
+        if (plan.theta)
+            AQ_HIP(hipMemcpyAsync(v.theta, B.h_theta + off[c] * NP, sizeof(double) * NP * m, hipMemcpyHostToDevice, s));
+        AQ_HIP(hipMemcpyAsync(v.bounds, B.h_bounds + off[c], sizeof(double2) * m, hipMemcpyHostToDevice, s));
+        return AQ_OK;
+    }
+    // size classes from the estimates, the bounds (and theta) into size order; preset: the scatter also sets
+    // the launch's job size from the estimates (AQ_F_* values are the kernels' FIDs)
+    int pre(int c, hipStream_t s) {
+        const BatchRings::View v = B.at(c);
+        const int m = plan.chunks[c];
+        const unsigned blocks = (unsigned)((m + 255) / 256);
+        unsigned* const key = B.key;
+        if (plan.theta)
+            hipLaunchKernelGGL(k_batch_estimate_params, dim3(blocks), dim3(256), 0, s, v.bounds, (const double*)v.theta, m,
+                               eps, key, v.cnt, v.est, ctx->d_tab);
+        else
+            with_fid(integrand, [&](auto F) {
+                hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, v.bounds, m, eps, key,
+                                   v.cnt, v.est, ctx->d_tab);
+            });
+        hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, s, v.bounds, key, m, v.cnt, v.cnt + EST_KEYS,
+                           v.sorted, v.perm, v.cnt_next, v.est, v.est_next, plan.preset[c] ? ctx->d_hint : nullptr,
+                           (unsigned)(ctx->grid * NW));
+        if (plan.theta)
+            hipLaunchKernelGGL(k_batch_scatter_theta, dim3((unsigned)(((size_t)m * NP + 255) / 256)), dim3(256), 0, s,
+                               (const double*)v.theta, (const unsigned*)v.perm, m, (int)NP, v.thsorted);
+        AQ_HIP(hipGetLastError());
+        return AQ_OK;
+    }
+    int launch_chunk(int c) {
+        const BatchRings::View v = B.at(c);
+        LaunchArgs g;   // (no histograms: hist stays false)
+        g.integrand = integrand;
+        g.k = plan.chunks[c];
+        g.a = a + off[c];
+        g.b = b + off[c];
+        g.eps = eps;
+        g.dev_bounds = plan.sorted[c] ? v.sorted : v.bounds;
+        g.dev_theta = plan.sorted[c] ? v.thsorted : v.theta;
+        g.err = plan.err;
+        g.heap = true;
+        ctx->hint.preset = plan.preset[c];
+        const int rc = launch(ctx, g);
+        ctx->hint.preset = false;
+        return rc;
+    }
+    // (k_gather_reset writes size-ordered slots back in input order)
+    int gather(int c) {
+        const BatchRings::View v = B.at(c);
+        return gather_clean(ctx, plan.chunks[c], v.rows, v.errrows, plan.sorted[c] ? v.perm : nullptr);
+    }
+    int d2h(int c, hipStream_t s) {
+        const BatchRings::View v = B.at(c);
+        const size_t m = (size_t)plan.chunks[c];
+        AQ_HIP(hipMemcpyAsync(B.h_rows + 4 * off[c], v.rows, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, s));
+        if (plan.err)
+            AQ_HIP(hipMemcpyAsync(B.h_errrows + 2 * off[c], v.errrows, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, s));
+        return AQ_OK;
+    }
+    void unpack(int c) {
+        errbits |= unpack_rows(ctx, (size_t)plan.chunks[c], B.h_rows + 4 * off[c], 4,
+                               plan.err ? B.h_errrows + 2 * off[c] : nullptr, 2, out.from(off[c]),
+                               [](size_t, const double*, size_t) {});
+    }
+};
+
+// A bad bound fails the call (AQ_EINVAL) after the chunks before it ran; the outputs are then unspecified.
 static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, const double* theta, double eps,
                      int integrand, double* area, uint64_t* accepted, uint64_t* tasks, bool err = false,
                      double* err_abs = nullptr, double* err_signed = nullptr) {
-    // Batch front end (SURVEY config 3): up to MAXK integrals per persistent launch, every integral
-    // with its own slot. Three streams (r05; profiles/r05a/c3_timeline_r04code.json had the launches
-    // wait ~0.5 ms per chunk for a reset, a bounds copy, a full-width gather and a rows copy):
-    //   * s_h2d copies chunk c + 1's bounds (checked and staged by the host while chunk c runs) into
-    //     their own device rows, so the launch finds them in place (launch_stream dev_bounds);
-    //   * the context's stream runs the launches, each followed by k_gather_reset, which writes the
-    //     chunk's rows AND returns its slots to zero (no k_reset before the next launch);
-    //   * s_d2h copies each chunk's rows back while the next chunk runs; the host unpacks chunk c - 1
-    //     while chunk c runs;
-    //   * s_pre runs each chunk's size-order pre-pass as soon as its bounds are on the device: chunk
-    //     c + 1's waits for the CUs chunk c's launch frees and then runs beside chunk c's gather
-    //     (r06: the two had run one after the other between the launches).
-    // A small first chunk starts the device early; a small last chunk shortens the copy-back after it.
-    // A bad bound fails the call (AQ_EINVAL) after the chunks before it ran; the outputs are then
-    // unspecified.
     if (!ctx || (n && (!a || !b))) return AQ_EINVAL;
     const bool par = integrand == AQ_F_PARAM;
-    constexpr size_t NP = (size_t)param::nparams;
     if (par ? !theta : !integrand_ok(integrand)) return AQ_EINVAL;
     if (!(eps >= 0.0)) return AQ_EINVAL;
     if (n == 0) return AQ_OK;
@@ -1438,252 +1678,61 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
     AQ_HIP(hipSetDevice(ctx->device));
     const std::vector<int> chunks = batch_chunks(n, (size_t)std::max(0, env_int("AQ_BATCH_FIRST", AQ_BATCH_FIRST)),
                                                  (size_t)std::max(0, env_int("AQ_BATCH_LAST", AQ_BATCH_LAST)));
-    const size_t nc = chunks.size();
-    const size_t rows = (size_t)*std::max_element(chunks.begin(), chunks.end());   // <= MAXK
-    // the device rings hold two chunks of `rows`, the pinned copies the whole call (grow-only, aq_ctx)
-    AQ_HIP(ctx->d_batch.grow(8 * rows));
-    AQ_HIP(ctx->d_bbounds.grow(2 * rows));
-    AQ_HIP(ctx->d_bsorted.grow(2 * rows));
-    AQ_HIP(ctx->d_bkey.grow(rows));
-    AQ_HIP(ctx->d_bperm.grow(2 * rows));
-    AQ_HIP(ctx->h_batch.grow(4 * n));
-    AQ_HIP(ctx->h_bbounds.grow(n));
-    if (par) {
-        AQ_HIP(ctx->d_btheta.grow(NP * 2 * rows));
-        AQ_HIP(ctx->d_bthsorted.grow(NP * 2 * rows));
-        AQ_HIP(ctx->h_btheta.grow(NP * n));
-    }
-    if (err) {
-        AQ_HIP(ctx->d_berr.grow(4 * rows));
-        AQ_HIP(ctx->h_berr.grow(2 * n));
-    }
-    // chunk c's device rings: bounds, rows, theta, error sums and the size order at parity c & 1, this call's
-    // `rows` apart (every ring holds at least that; the keys live only between a chunk's two pre-pass
-    // kernels, which run in order on s_pre)
-    const size_t R = rows;
-    auto dev_err_rows_of = [&](size_t c) { return ctx->d_berr + 2 * (c & 1u) * R; };
-    auto dev_theta_of = [&](size_t c) { return ctx->d_btheta + (c & 1u) * R * NP; };
-    auto thsorted_of = [&](size_t c) { return ctx->d_bthsorted + (c & 1u) * R * NP; };
-    auto dev_bounds_of = [&](size_t c) { return ctx->d_bbounds + (c & 1u) * R; };
-    auto dev_rows_of = [&](size_t c) { return ctx->d_batch + 4 * (c & 1u) * R; };
-    auto sorted_of = [&](size_t c) { return ctx->d_bsorted + (c & 1u) * R; };
-    auto perm_of = [&](size_t c) { return ctx->d_bperm + (c & 1u) * R; };
-    // size classes: counts + cursors per chunk parity (k_batch_scatter zeroes the other parity's)
-    AQ_HIP(ctx->d_bcnt.grow(4 * EST_KEYS));
-    AQ_HIP(ctx->d_best.grow(2));
-    // chunks in size order (largest trees first: the launch's tail is its smallest jobs), unless
-    // AQ_BATCH_SORT=0; chunks small enough for the per-CU instance keep their order (their bounds
-    // travel as kernel arguments)
     const bool sort = env_int("AQ_BATCH_SORT", 1) != 0;
+    // (preset while the workload is fresh: no measured hint for this integrand and tolerance)
+    const bool fresh = ctx->gsplit_env <= 0 && !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps &&
+                                                 ctx->hint.nshards == 1);
+    const BatchPlan plan = batch_plan(chunks, sort, par, err, fresh);
+    int rc = ctx->batch.grow((size_t)*std::max_element(chunks.begin(), chunks.end()), n, par, err);
+    if (rc) return rc;
     for (Stream* s : {&ctx->s_h2d, &ctx->s_d2h, &ctx->s_pre})
         if (!*s) AQ_HIP(s->create());
-    std::vector<size_t> off(nc + 1, 0);
-    for (size_t c = 0; c < nc; ++c) off[c + 1] = off[c] + (size_t)chunks[c];
-    // four events per chunk: bounds on the device, rows gathered, rows on the host, size order done;
-    // and one for the work already on the context's stream (the pre-pass stream starts behind it: a
-    // caller's pending launch updates the job-size hint the first pre-pass may preset), and one behind the
-    // zeroing of the size-class counts. (Destroyed on return, after every stream was synchronised.)
-    std::vector<Event> ev(4 * nc + 2);
+    const hipStream_t streams[] = {ctx->stream, ctx->s_h2d, ctx->s_d2h, ctx->s_pre};   // by BStream
+    // (destroyed on return, after every stream was synchronised: the plan's DRAIN)
+    std::vector<Event> ev((size_t)plan.n_events());
     for (Event& e : ev) AQ_HIP(e.create(hipEventDisableTiming));
-    auto ev_h2d = [&](size_t c) -> hipEvent_t { return ev[4 * c]; };
-    auto ev_gath = [&](size_t c) -> hipEvent_t { return ev[4 * c + 1]; };
-    auto ev_d2h = [&](size_t c) -> hipEvent_t { return ev[4 * c + 2]; };
-    auto ev_pre = [&](size_t c) -> hipEvent_t { return ev[4 * c + 3]; };
-    const hipEvent_t ev_start = ev[4 * nc], ev_zero = ev[4 * nc + 1];
-    unsigned errbits = 0;
-    std::vector<char> sorted_chunk(nc, 0);
-    // rows [i0, i1) into the outputs (k_gather_reset wrote size-ordered slots back in order)
-    auto unpack_rows = [&](size_t i0, size_t i1) {
-        unsigned e = 0;
-        for (size_t i = i0; i < i1; ++i) {
-            const double* row = ctx->h_batch + 4 * i;
-            if (area) area[i] = row[0];
-            if (tasks) tasks[i] = (uint64_t)row[1];
-            if (accepted) accepted[i] = (uint64_t)row[2];
-            e |= (unsigned)row[3];
-            if (err_abs) err_abs[i] = ctx->h_berr[2 * i];
-            if (err_signed) err_signed[i] = ctx->h_berr[2 * i + 1];
+    BatchCall call{ctx, ctx->batch, plan, std::vector<size_t>(chunks.size() + 1, 0), a, b, theta, eps, integrand,
+                   RowsOut{area, accepted, tasks, err_abs, err_signed}};
+    for (size_t c = 0; c < chunks.size(); ++c) call.off[c + 1] = call.off[c] + (size_t)chunks[c];
+    static_assert(AQ_OK == 0, "BatchWalk's success code");
+    BatchWalk walk;   // which steps a failure leaves out
+    for (const BatchStep& s : plan.steps) {
+        if (!walk.runs(s)) continue;
+        const int c = s.chunk;
+        const hipStream_t st = s.stream == BStream::HOST ? nullptr : streams[(int)s.stream];
+        int r = AQ_OK;
+        for (int w : s.wait)
+            if (w >= 0 && (st ? hipStreamWaitEvent(st, ev[w], 0) : hipEventSynchronize(ev[w])) != hipSuccess) r = AQ_EHIP;
+        if (r == AQ_OK) switch (s.kind) {
+            case BKind::START: case BKind::FENCE: break;   // their event is all they do
+            case BKind::ZERO: r = call.zero(st); break;
+            case BKind::STAGE:
+                if (c == 0) mark("setup", -1);
+                r = call.stage(c);
+                break;
+            case BKind::H2D: r = call.h2d(c, st), mark("staged", c); break;
+            case BKind::PRE: r = call.pre(c, st); break;
+            case BKind::LAUNCH: r = call.launch_chunk(c), mark("launched", c); break;
+            case BKind::GATHER: r = call.gather(c); break;
+            case BKind::D2H: r = call.d2h(c, st); break;
+            case BKind::WAIT: mark("rows on host", c); break;
+            case BKind::UNPACK: call.unpack(c), mark("unpacked", c); break;
+            case BKind::DRAIN:   // every enqueued chunk finishes before the buffers can be reused or the events destroyed
+                for (hipStream_t x : streams)
+                    if (hipStreamSynchronize(x) != hipSuccess) r = AQ_EHIP;
+                mark("device done", -1);
+                break;
         }
-        return e;
-    };
-    // chunk c's rows on several host threads (the last chunk's after the device is done; the others'
-    // while the next chunk runs, beside its staging, which must stay shorter than a launch)
-    auto unpack = [&](size_t c) {
-        std::vector<unsigned> e(64, 0u);
-        host_parallel(ctx, off[c + 1] - off[c], 8192,
-                      [&](size_t i0, size_t i1, size_t p) { e[p] = unpack_rows(off[c] + i0, off[c] + i1); });
-        for (unsigned x : e) errbits |= x;
-    };
-    // chunk c's order is preset (sets the launch's job size) while the workload is fresh
-    auto sorted_at = [&](size_t c) { return sort && chunks[c] >= 64; };
-    auto preset_at = [&](size_t c) {
-        return sorted_at(c) && ctx->gsplit_env <= 0 &&
-               !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps && ctx->hint.nshards == 1);
-    };
-    // the size-order pre-pass of chunk c on s_pre (after its bounds arrived; the launch waits for it)
-    // (preset: a fresh workload -- no measured hint for this integrand and tolerance: the pre-pass sets
-    // the launch's job size from its estimates; AQ_F_* values are the kernels' FIDs)
-    // (its sorted / perm parity was last read by chunk c - 2's launch and gather, which the bounds'
-    // copy for chunk c already waited for)
-    // The first chunk's copy and pre-pass and the last chunk's copy back run on the context's stream
-    // itself: in order with the launches, where a wait across streams costs the device ~20-60 us
-    // between the two operations (profiles/r06o: copy -> estimate 18 us, scatter -> launch 17 us,
-    // gather -> last copy back 62 us, against ~7 us in order). The middle chunks' keep their own
-    // streams, whose work overlaps the previous launch.
-    auto h2d_stream = [&](size_t c) -> hipStream_t { return c == 0 ? ctx->stream : ctx->s_h2d; };
-    auto pre_stream = [&](size_t c) -> hipStream_t { return c == 0 ? ctx->stream : ctx->s_pre; };
-    auto d2h_stream = [&](size_t c) -> hipStream_t { return c + 1 == nc ? ctx->stream : ctx->s_d2h; };
-    auto order = [&](size_t c, bool preset) -> int {
-        const int m = chunks[c];
-        const hipStream_t sp = pre_stream(c);
-        if (hipStreamWaitEvent(sp, ev_h2d(c), 0) != hipSuccess) return AQ_EHIP;
-        // (chunk 1's estimate adds into the counts chunk 0's scatter zeroed, on the context's stream -- or,
-        // behind an unsorted chunk 0, into the counts the call zeroed there: ev_zero. Later chunks follow
-        // both through ev_gath(c - 2), which their bounds' copy waited for)
-        if (c == 1 && hipStreamWaitEvent(sp, sorted_at(0) ? ev_pre(0) : ev_zero, 0) != hipSuccess) return AQ_EHIP;
-        const unsigned blocks = (unsigned)((m + 255) / 256);
-        unsigned* const cnt = ctx->d_bcnt + 2 * EST_KEYS * (c & 1u);
-        unsigned* const cnt_next = ctx->d_bcnt + 2 * EST_KEYS * ((c + 1) & 1u);
-        if (par)
-            hipLaunchKernelGGL(k_batch_estimate_params, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c),
-                               (const double*)dev_theta_of(c), m, eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
-        else
-            with_fid(integrand, [&](auto F) {
-                hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c), m,
-                                   eps, ctx->d_bkey, cnt, ctx->d_best + (c & 1u), ctx->d_tab);
-            });
-        hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, sp, dev_bounds_of(c),
-                           ctx->d_bkey, m, cnt, cnt + EST_KEYS, sorted_of(c),
-                           perm_of(c), cnt_next, ctx->d_best + (c & 1u), ctx->d_best + ((c + 1) & 1u),
-                           preset ? ctx->d_hint : nullptr, (unsigned)(ctx->grid * NW));
-        if (par)
-            hipLaunchKernelGGL(k_batch_scatter_theta, dim3((unsigned)(((size_t)m * NP + 255) / 256)), dim3(256), 0, sp,
-                               (const double*)dev_theta_of(c), (const unsigned*)perm_of(c), m, (int)NP, thsorted_of(c));
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev_pre(c), sp) != hipSuccess) return AQ_EHIP;
-        return AQ_OK;
-    };
-    // check chunk c's bounds, stage them and copy them to the device on s_h2d (on several host threads:
-    // the first chunk's is the only host work before the device starts)
-    auto stage_rows = [&](size_t i0, size_t i1) {
-        for (size_t i = i0; i < i1; ++i) {
-            if (par) {
-                if (!params_ok(a[i], b[i], theta + i * NP)) return false;
-                for (size_t j = 0; j < NP; ++j) ctx->h_btheta[i * NP + j] = theta[i * NP + j];
-            } else if (!bounds_ok(integrand, a[i], b[i])) {
-                return false;
-            }
-            ctx->h_bbounds[i] = make_double2(a[i], b[i]);
-        }
-        return true;
-    };
-    auto stage = [&](size_t c) -> int {
-        std::vector<char> ok(64, 1);
-        host_parallel(ctx, (size_t)chunks[c], 8192,
-                      [&](size_t i0, size_t i1, size_t p) { ok[p] = stage_rows(off[c] + i0, off[c] + i1); });
-        for (char o : ok)
-            if (!o) return AQ_EINVAL;
-        // the ring slot chunk c - 2 used: its readers (size pre-pass, launch) are done at its gather
-        if (c >= 2 && hipStreamWaitEvent(ctx->s_h2d, ev_gath(c - 2), 0) != hipSuccess) return AQ_EHIP;
-        if (par && hipMemcpyAsync(dev_theta_of(c), ctx->h_btheta + off[c] * NP, sizeof(double) * NP * (size_t)chunks[c],
-                                  hipMemcpyHostToDevice, h2d_stream(c)) != hipSuccess)
-            return AQ_EHIP;
-        if (hipMemcpyAsync(dev_bounds_of(c), ctx->h_bbounds + off[c], sizeof(double2) * (size_t)chunks[c],
-                           hipMemcpyHostToDevice, h2d_stream(c)) != hipSuccess ||
-            hipEventRecord(ev_h2d(c), h2d_stream(c)) != hipSuccess)
-            return AQ_EHIP;
-        return AQ_OK;
-    };
-    size_t ran = 0;   // chunks enqueued
-    int rc = AQ_OK;
-    // (s_pre starts once the work already queued on the context's stream is done -- a pending launch may
-    // still read or write the hint the first scatter may preset. The counts are zeroed on the context's
-    // stream, where chunk 0's pre-pass runs; behind an unsorted chunk 0 the first pre-pass is chunk 1's on
-    // s_pre, which waits for ev_zero: order)
-    if (hipEventRecord(ev_start, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->s_pre, ev_start, 0) != hipSuccess)
-        rc = AQ_EHIP;
-    if (rc == AQ_OK && sort &&
-        (hipMemsetAsync(ctx->d_bcnt, 0, sizeof(unsigned) * 4 * EST_KEYS, pre_stream(0)) != hipSuccess ||
-         hipMemsetAsync(ctx->d_best, 0, sizeof(double) * 2, pre_stream(0)) != hipSuccess ||
-         (!sorted_at(0) && hipEventRecord(ev_zero, pre_stream(0)) != hipSuccess)))
-        rc = AQ_EHIP;
-    mark("setup", -1);
-    if (rc == AQ_OK) rc = stage(0);
-    mark("staged", 0);
-    if (rc == AQ_OK && sorted_at(0)) rc = order(0, preset_at(0));
-    for (size_t c = 0; c < nc && rc == AQ_OK; ++c) {
-        const int m = chunks[c];
-        sorted_chunk[c] = sorted_at(c);
-        if (hipStreamWaitEvent(ctx->stream, sorted_chunk[c] ? ev_pre(c) : ev_h2d(c), 0) != hipSuccess) {
-            rc = AQ_EHIP;
-            break;
-        }
-        LaunchArgs g;   // (no histograms: hist stays false)
-        g.integrand = integrand;
-        g.k = m;
-        g.a = a + off[c];
-        g.b = b + off[c];
-        g.eps = eps;
-        g.dev_bounds = sorted_chunk[c] ? sorted_of(c) : dev_bounds_of(c);
-        if (par) g.dev_theta = sorted_chunk[c] ? thsorted_of(c) : dev_theta_of(c);
-        g.err = err;
-        g.heap = true;
-        ctx->hint.preset = preset_at(c);
-        rc = launch(ctx, g);
-        ctx->hint.preset = false;
-        mark("launched", (long)c);
-        if (rc) break;
-        // the rows' ring slot: chunk c - 2's copy to the host must be done before they are overwritten
-        if (c >= 2 && hipStreamWaitEvent(ctx->stream, ev_d2h(c - 2), 0) != hipSuccess) { rc = AQ_EHIP; break; }
-        hipLaunchKernelGGL(k_gather_reset, dim3((m + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts,
-                           ctx->grid, 0, m, dev_rows_of(c), sorted_chunk[c] ? perm_of(c) : nullptr);
-        if (err)   // (its rows' ring slot is free as the rows' is: the wait for chunk c - 2's copy above)
-            hipLaunchKernelGGL(k_gather_err, dim3((m + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, m,
-                               dev_err_rows_of(c), sorted_chunk[c] ? perm_of(c) : nullptr);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev_gath(c), ctx->stream) != hipSuccess) {
-            rc = AQ_EHIP;
-            break;
-        }
-        if (err) memset(ctx->err_dirty, 0, (size_t)m);   // k_gather_err zeroed them
-        memset(ctx->dirty, 0, (size_t)m);   // k_gather_reset zeroed them
-        memset(ctx->parts_dirty, 0, (size_t)m);
-        ++ran;
-        // the next chunk's bounds while this one runs (a bad bound stops the batch here), and its size
-        // order behind them
-        int rc_next = c + 1 < nc ? stage(c + 1) : AQ_OK;
-        if (c + 1 < nc) mark("staged", (long)c + 1);
-        if (rc_next == AQ_OK && c + 1 < nc && sorted_at(c + 1)) rc_next = order(c + 1, preset_at(c + 1));
-        if (hipStreamWaitEvent(d2h_stream(c), ev_gath(c), 0) != hipSuccess ||
-            hipMemcpyAsync(ctx->h_batch + 4 * off[c], dev_rows_of(c), sizeof(double) * 4 * (size_t)m,
-                           hipMemcpyDeviceToHost, d2h_stream(c)) != hipSuccess ||
-            (err && hipMemcpyAsync(ctx->h_berr + 2 * off[c], dev_err_rows_of(c), sizeof(double) * 2 * (size_t)m,
-                                   hipMemcpyDeviceToHost, d2h_stream(c)) != hipSuccess) ||
-            hipEventRecord(ev_d2h(c), d2h_stream(c)) != hipSuccess) {
-            rc = AQ_EHIP;
-            break;
-        }
-        if (c > 0) {   // the previous chunk's rows, while this one runs
-            if (hipEventSynchronize(ev_d2h(c - 1)) != hipSuccess) { rc = AQ_EHIP; break; }
-            mark("rows on host", (long)c - 1);
-            unpack(c - 1);
-            mark("unpacked", (long)c - 1);
-        }
-        rc = rc_next;
+        if (r == AQ_OK && s.record >= 0 && hipEventRecord(ev[s.record], st) != hipSuccess) r = AQ_EHIP;
+        walk.done(s, r);
     }
-    // every enqueued chunk finishes before the buffers can be reused or the events destroyed
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
-    if (hipStreamSynchronize(ctx->s_d2h) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
-    if (hipStreamSynchronize(ctx->s_h2d) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
-    if (hipStreamSynchronize(ctx->s_pre) != hipSuccess && rc == AQ_OK) rc = AQ_EHIP;
-    mark("device done", -1);
-    if (rc) return rc;
-    if (ran) unpack(ran - 1);
-    mark("unpacked", (long)ran - 1);
+    if (walk.rc) return walk.rc;
     if (trace) {
         fprintf(stderr, "aq_integrate_batch n=%zu:", n);
         for (auto& m : tr) fprintf(stderr, " [%s %.1f us]", m.first.c_str(), m.second);
         fprintf(stderr, "\n");
     }
-    return err_from_bits(errbits);
+    return err_from_bits(call.errbits);
 }
 
 int aq_integrate_batch(aq_ctx* ctx, size_t n, const double* a, const double* b, double eps, int integrand,
@@ -1706,36 +1755,10 @@ int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double*
 }
 
 // ---- tolerance-driven batch (aq_integrate_batch_tol) -----------------------------------------------------
-// The buffers of a block of `rows` integrals, on the first such call (a context that never made one holds none
-// of them: aq_ctx_device_bytes does not move until then); grow-only.
-static int tol_ensure(aq_ctx* ctx, size_t rows, bool par) {
-    constexpr size_t NP = (size_t)param::nparams;
-    AQ_HIP(ctx->d_tbounds.grow(2 * rows));
-    AQ_HIP(ctx->d_tidx.grow(2 * rows));
-    AQ_HIP(ctx->d_trows.grow(4 * rows));
-    AQ_HIP(ctx->d_terr.grow(2 * rows));
-    AQ_HIP(ctx->d_tflag.grow(rows));
-    AQ_HIP(ctx->d_tcnt.grow((rows + TOL_T - 1) / TOL_T));
-    AQ_HIP(ctx->d_ttsum.grow((rows + TOL_T - 1) / TOL_T));
-    AQ_HIP(ctx->d_tres.grow(TOL_REC * rows));
-    AQ_HIP(ctx->h_tbounds.grow(rows));
-    AQ_HIP(ctx->h_tres.grow(TOL_REC * rows));
-    if (par) {
-        AQ_HIP(ctx->d_ttheta.grow(2 * NP * rows));
-        AQ_HIP(ctx->h_ttheta.grow(NP * rows));
-    }
-    if (!ctx->h_tsurv) {
-        AQ_HIP(ctx->h_tsurv.alloc(1, true, hipHostMallocCoherent | hipHostMallocMapped));
-        AQ_HIP(hipHostGetDevicePointer((void**)&ctx->d_tsurv, ctx->h_tsurv, 0));
-    }
-    return AQ_OK;
-}
-
 // a call's outputs (any may be null)
 struct TolOut {
-    double* area;
-    uint64_t *accepted, *tasks;
-    double *err_abs, *err_signed, *eps_used;
+    RowsOut rows;
+    double* eps_used;
     int32_t* rounds;
 };
 
@@ -1746,28 +1769,14 @@ static int tol_block(aq_ctx* ctx, size_t m, size_t R, const double* a, const dou
                      int integrand, const aq_tol& t, const TolOut& o, unsigned* errbits, bool* noconv) {
     const bool par = integrand == AQ_F_PARAM;
     constexpr size_t NP = (size_t)param::nparams;
-    // 1. check and stage once (on the host pool), copy once into half 0, rows' indices 0 .. m-1
-    {
-        std::vector<char> ok(64, 1);
-        host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
-            for (size_t i = i0; i < i1; ++i) {
-                if (par ? !params_ok(a[i], b[i], theta + i * NP) : !bounds_ok(integrand, a[i], b[i])) {
-                    ok[p] = 0;
-                    return;
-                }
-                ctx->h_tbounds[i] = make_double2(a[i], b[i]);
-                if (par)
-                    for (size_t j = 0; j < NP; ++j) ctx->h_ttheta[i * NP + j] = theta[i * NP + j];
-            }
-        });
-        for (char c : ok)
-            if (!c) return AQ_EINVAL;
-    }
-    AQ_HIP(hipMemcpyAsync(ctx->d_tbounds, ctx->h_tbounds, sizeof(double2) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (par)
-        AQ_HIP(hipMemcpyAsync(ctx->d_ttheta, ctx->h_ttheta, sizeof(double) * NP * m, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_tol_init, dim3((unsigned)((m + TOL_T - 1) / TOL_T)), dim3(TOL_T), 0, ctx->stream,
-                       ctx->d_tidx.get(), (int)m, ctx->d_hint.get());
+    const TolBufs& T = ctx->tol;
+    // 1. check and stage once, copy once into half 0, rows' indices 0 .. m-1
+    int rc = check_and_stage(ctx, integrand, m, a, b, theta, T.h_bounds, T.h_theta);
+    if (rc) return rc;
+    AQ_HIP(hipMemcpyAsync(T.bounds, T.h_bounds, sizeof(double2) * m, hipMemcpyHostToDevice, ctx->stream));
+    if (par) AQ_HIP(hipMemcpyAsync(T.theta, T.h_theta, sizeof(double) * NP * m, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_tol_init, dim3((unsigned)((m + TOL_T - 1) / TOL_T)), dim3(TOL_T), 0, ctx->stream, T.idx.get(),
+                       (int)m, ctx->d_hint.get());
     AQ_HIP(hipGetLastError());
     // the trapezoid rule's d scales as h^3, so a leaf's width as eps^(1/3): a round's trees are about
     // shrink^(1/3) times the round before's
@@ -1779,9 +1788,9 @@ static int tol_block(aq_ctx* ctx, size_t m, size_t R, const double* a, const dou
     double eps = t.eps0;
     for (int r = 1; k > 0; ++r, eps /= t.shrink) {
         const bool last = r == t.max_rounds;
-        const double2* bounds = ctx->d_tbounds + (size_t)half * R;
-        const double* th = par ? ctx->d_ttheta + (size_t)half * R * NP : nullptr;
-        const unsigned* idx = ctx->d_tidx + (size_t)half * R;
+        const double2* bounds = T.bounds + (size_t)half * R;
+        const double* th = par ? T.theta + (size_t)half * R * NP : nullptr;
+        const unsigned* idx = T.idx + (size_t)half * R;
         // 2. the round: one ERR launch of the k live rows, then the batch front end's two gathers
         LaunchArgs g;
         g.integrand = integrand;
@@ -1796,64 +1805,46 @@ static int tol_block(aq_ctx* ctx, size_t m, size_t R, const double* a, const dou
         g.heap = true;
         // the job size comes from the hint the kernels before this launch preset (per-CU launches have none)
         ctx->hint.preset = k >= PCU_MAXK;
-        int rc = launch(ctx, g);
+        rc = launch(ctx, g);
         ctx->hint.preset = false;
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gather_reset, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts,
-                           ctx->grid, 0, k, ctx->d_trows.get(), (const unsigned*)nullptr);
-        hipLaunchKernelGGL(k_gather_err, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, k,
-                           ctx->d_terr.get(), (const unsigned*)nullptr);
-        AQ_HIP(hipGetLastError());
-        memset(ctx->err_dirty, 0, (size_t)k);   // the gathers zeroed the slots
-        memset(ctx->dirty, 0, (size_t)k);
-        memset(ctx->parts_dirty, 0, (size_t)k);
+        if ((rc = gather_clean(ctx, k, T.rows, T.err, nullptr))) return rc;
         // 3. test and retire; the survivors into the other half, their count to the host
         const unsigned nb = (unsigned)((k + TOL_T - 1) / TOL_T);
-        hipLaunchKernelGGL(k_tol_test, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const double*)ctx->d_trows,
-                           (const double*)ctx->d_terr, idx, k, t.epsabs, t.epsrel, eps, r, last ? 1 : 0, ctx->d_tres.get(),
-                           ctx->d_tflag.get(), ctx->d_tcnt.get(), ctx->d_ttsum.get());
+        hipLaunchKernelGGL(k_tol_test, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const double*)T.rows, (const double*)T.err,
+                           idx, k, t.epsabs, t.epsrel, eps, r, last ? 1 : 0, T.res.get(), T.flag.get(), T.cnt.get(),
+                           T.tsum.get());
         AQ_HIP(hipGetLastError());
         if (last) break;   // every row retired
         const int other = half ^ 1;
-        hipLaunchKernelGGL(k_tol_compact, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const unsigned char*)ctx->d_tflag,
-                           (const unsigned*)ctx->d_tcnt, k, bounds, th, idx, ctx->d_tbounds + (size_t)other * R,
-                           par ? ctx->d_ttheta + (size_t)other * R * NP : nullptr, ctx->d_tidx + (size_t)other * R,
-                           par ? (int)NP : 0, ctx->d_tsurv, (const double*)ctx->d_ttsum, growth, ctx->d_hint.get(),
-                           (unsigned)(ctx->grid * ERR_NW));
+        hipLaunchKernelGGL(k_tol_compact, dim3(nb), dim3(TOL_T), 0, ctx->stream, (const unsigned char*)T.flag,
+                           (const unsigned*)T.cnt, k, bounds, th, idx, T.bounds + (size_t)other * R,
+                           par ? T.theta + (size_t)other * R * NP : nullptr, T.idx + (size_t)other * R, par ? (int)NP : 0,
+                           T.d_surv, (const double*)T.tsum, growth, ctx->d_hint.get(), (unsigned)(ctx->grid * ERR_NW));
         AQ_HIP(hipGetLastError());
         // 4. the host's one look per round
         AQ_HIP(hipStreamSynchronize(ctx->stream));
-        const unsigned left = __atomic_load_n(&ctx->h_tsurv->count, __ATOMIC_ACQUIRE);
+        const unsigned left = __atomic_load_n(&T.h_surv->count, __ATOMIC_ACQUIRE);
         if (left > (unsigned)k) return AQ_EHIP;   // (cannot happen: survivors are some of the k rows)
         k = (int)left;
         half = other;
         if (k < PCU_MAXK)
             for (int j = 0; j < k; ++j) {
-                const unsigned i = ctx->h_tsurv->idx[j];
+                const unsigned i = T.h_surv->idx[j];
                 if (i >= m) return AQ_EHIP;
                 ha[j] = a[i], hb[j] = b[i];
             }
     }
     // 5. the block's records: one copy, unpacked on the host pool
-    AQ_HIP(hipMemcpyAsync(ctx->h_tres, ctx->d_tres, sizeof(double) * TOL_REC * m, hipMemcpyDeviceToHost, ctx->stream));
+    // (a record: the row's four fields, its error pair, eps_used, rounds)
+    AQ_HIP(hipMemcpyAsync(T.h_res, T.res, sizeof(double) * TOL_REC * m, hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<unsigned> e(64, 0u);
     std::vector<char> nc(64, 0);
-    host_parallel(ctx, m, 8192, [&](size_t i0, size_t i1, size_t p) {
-        for (size_t i = i0; i < i1; ++i) {
-            const double* rec = ctx->h_tres + TOL_REC * i;
-            if (o.area) o.area[i] = rec[0];
-            if (o.tasks) o.tasks[i] = (uint64_t)rec[1];
-            if (o.accepted) o.accepted[i] = (uint64_t)rec[2];
-            e[p] |= (unsigned)rec[3];
-            if (o.err_abs) o.err_abs[i] = rec[4];
-            if (o.err_signed) o.err_signed[i] = rec[5];
-            if (o.eps_used) o.eps_used[i] = rec[6];
-            if (o.rounds) o.rounds[i] = (int32_t)rec[7];
-            if (rec[7] < 0.0) nc[p] = 1;
-        }
+    *errbits |= unpack_rows(ctx, m, T.h_res, TOL_REC, T.h_res + 4, TOL_REC, o.rows, [&](size_t i, const double* rec, size_t p) {
+        if (o.eps_used) o.eps_used[i] = rec[6];
+        if (o.rounds) o.rounds[i] = (int32_t)rec[7];
+        if (rec[7] < 0.0) nc[p] = 1;
     });
-    for (unsigned x : e) *errbits |= x;
     for (char c : nc) *noconv |= c != 0;
     return AQ_OK;
 }
@@ -1868,14 +1859,13 @@ int aq_integrate_batch_tol(aq_ctx* ctx, size_t n, const double* a, const double*
     constexpr size_t NP = (size_t)param::nparams;
     AQ_HIP(hipSetDevice(ctx->device));
     const size_t R = std::min(n, (size_t)tol_block_rows(env_int("AQ_TOL_BLOCK", 0)));
-    int rc = tol_ensure(ctx, R, integrand == AQ_F_PARAM);
+    int rc = ctx->tol.ensure(R, integrand == AQ_F_PARAM);
     if (rc) return rc;
     unsigned errbits = 0;
     bool noconv = false;
-    auto at = [](auto* p, size_t off) { return p ? p + off : p; };
+    const RowsOut rows{area, accepted, tasks, err_abs, err_signed};
     for (size_t off = 0; off < n; off += R) {
-        const TolOut o{at(area, off), at(accepted, off), at(tasks, off), at(err_abs, off), at(err_signed, off),
-                       at(eps_used, off), at(rounds, off)};
+        const TolOut o{rows.from(off), eps_used ? eps_used + off : nullptr, rounds ? rounds + off : nullptr};
         rc = tol_block(ctx, std::min(R, n - off), R, a + off, b + off, theta ? theta + off * NP : nullptr, integrand, t, o,
                        &errbits, &noconv);
         if (rc) {

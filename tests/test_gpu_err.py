@@ -175,6 +175,31 @@ def test_batch_params(ctx, monkeypatch):
     _check_rows(area, tasks, acc, ea, es, w, slice(0, n), "input order")
 
 
+def test_batch_every_ring_twice(ctx, monkeypatch):
+    """468 integrals of the draw in chunks of 64, 128, 256 and 20: the smallest call in which every device ring
+    is written again at both parities (chunks 2 and 3) with theta and error rows travelling, and an unsorted last
+    chunk runs behind sorted ones. Twice on one context; then a bad bound in chunk 2 fails the call while chunk 1
+    runs, and the context's next call gives the first 64 rows of the earlier result bit for bit, error sums
+    included (the draw's trees have at most 945 tasks; 40 repetitions of this sequence gave the same bits every
+    time, on this code and on the one before it)."""
+    from ppls_amd import AquadError
+    n = 468
+    a, b, theta, w = er.draw_reference()
+    a, b, theta = a[:n].copy(), b[:n], theta[:n]
+    monkeypatch.setenv("AQ_BATCH_FIRST", "64")
+    for again in range(2):
+        area, tasks, acc, ea, es = ctx.integrate_batch_err(a, b, pr.DRAW_EPS, integrand=PARAM, theta=theta)
+        _check_rows(area, tasks, acc, ea, es, w, slice(0, n), ("468 rows", again))
+    a[64 + 128 + 5] = np.nan
+    with pytest.raises(AquadError):
+        ctx.integrate_batch_err(a, b, pr.DRAW_EPS, integrand=PARAM, theta=theta)
+    area1, tasks1, acc1, ea1, es1 = ctx.integrate_batch_err(a[:64], b[:64], pr.DRAW_EPS, integrand=PARAM, theta=theta[:64])
+    assert np.array_equal(tasks1, tasks[:64]) and np.array_equal(acc1, acc[:64])
+    assert np.array_equal(area1, area[:64])
+    assert np.array_equal(ea1, ea[:64]) and np.array_equal(es1, es[:64])
+    _check_rows(area1, tasks1, acc1, ea1, es1, w, slice(0, 64), "64 rows after the failed call")
+
+
 def test_batch_cosh4(ctx):
     a, b, w = er.batch_reference(2000, 1e-6)
     area, tasks, acc, ea, es = ctx.integrate_batch_err(a, b, 1e-6)
