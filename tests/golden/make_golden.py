@@ -18,6 +18,8 @@ Outputs (data only, no code of the reference):
   plugin_bits.npz x, F(x) of the AQ_F_USER plug-in (exp(-x*x), host libm) as uint64 bit patterns
   deep.json       eps 1e-14 .. 1e-16 cosh4 trees pinned by the reference binary's task totals
   sin_bits.npz    x, F(x) = sin(1.0/x) (config 4's F macro, host libm) as uint64 bit patterns
+  edges.json      trees at the edges of the documented domain (|x| = 170, subnormal areas, eps = 0, 2^-900, 2^900),
+                  on which the restated and the host-libm oracle modes must agree
 """
 import json
 import os
@@ -269,11 +271,57 @@ def deep():
         json.dump(out, f, indent=1)
 
 
+# Trees at the edges of the documented domain (include/aquad.h AQ_EINVAL): name, integrand, a, b, eps, and the
+# tasks, levels and area the oracle must give (written down from a run of both oracle modes; the step below
+# refuses to write anything else).
+_ULP1 = float(np.nextafter(1.0, 2.0))
+EDGES = [
+    ("user_tail_eps0", O.USER, 27.0, 27.5, 0.0, 597, 17, 4.638140063463870e-319),   # every area subnormal
+    ("user_zero_eps0", O.USER, 28.0, 40.0, 0.0, 1, 1, 0.0),                         # F underflows to 0 throughout
+    ("user_cross", O.USER, -6.0, 6.0, 1e-9, 5371, 14, 1.772453960562458545),
+    ("cosh_170", O.COSH4, 169.0, 170.0, 1e280, 82045, 17, 3.2065616394753214e293),
+    ("cosh_m170", O.COSH4, -170.0, -169.0, 1e280, 82045, 17, 3.2065616394753214e293),
+    ("cosh_pm170", O.COSH4, -170.0, 170.0, 1e285, 4843, 20, 6.532778077271939e293),
+    ("cosh_3ulp", O.COSH4, 1.0, 1.0 + 3 * 2.0 ** -52, 0.0, 5, 3, 3.776730228584413e-15),
+    ("cosh_ulp", O.COSH4, 1.0, _ULP1, 0.0, 1, 1, 1.2589100761948034e-15),
+    ("cosh_0tiny", O.COSH4, 0.0, 2.0 ** -900, 0.0, 1, 1, 1.1830521861667747e-271),
+    ("cosh_tiny", O.COSH4, 2.0 ** -900, 2.0 ** -899, 0.0, 1, 1, 1.1830521861667747e-271),
+    ("sin_neg", O.SIN_RECIP, -1.0, -1e-3, 1e-8, 11891, 22, -0.50406631068191603),
+    ("sin_big", O.SIN_RECIP, 2.0 ** 899, 2.0 ** 900, 1e-3, 9, 4, 0.69377140317542796),
+    ("sin_1e-8", O.SIN_RECIP, 1e-8, 1e-6, 1e-9, 715, 11, 2.4829501285150798e-9),
+]
+
+
+def edges():
+    """Trees at the edges of the documented domain: cosh^4 at |x| = 170, the Gaussian where F and its areas are
+    subnormal or zero, eps = 0, a negative sin(1/x) interval, bounds at 2^-900 and 2^900, intervals of one and three
+    ulps. The restated and the host-libm oracle modes must agree on every number and give the counts of EDGES.
+    Output: edges.json (bounds and areas also as hex floats)."""
+    names = {O.COSH4: "cosh4", O.SIN_RECIP: "sin_recip", O.USER: "gauss"}
+    out = {}
+    for name, integrand, a, b, eps, tasks, levels, area in EDGES:
+        r = O.integrate(integrand, a, b, eps, maxlev=128)
+        h = O.integrate(integrand, a, b, eps, mode=O.HOST_LIBM, maxlev=128)
+        assert (r.tasks, r.leaves, r.levels, r.tasks_per_level, r.leaves_per_level, r.area_quad_hi, r.area_quad_lo) == \
+            (h.tasks, h.leaves, h.levels, h.tasks_per_level, h.leaves_per_level, h.area_quad_hi, h.area_quad_lo), name
+        assert (r.tasks, r.levels) == (tasks, levels) and r.tasks == 2 * r.leaves - 1, (name, r.tasks, r.levels)
+        got = r.area_quad_hi + r.area_quad_lo
+        assert got == area or abs(got - area) <= 4e-16 * abs(area), (name, got, area)   # (the table's 16-17 digits)
+        out[name] = {"integrand": names[integrand], "a": a, "b": b, "eps": eps, "a_hex": float(a).hex(),
+                     "b_hex": float(b).hex(), "tasks": r.tasks, "leaves": r.leaves, "levels": r.levels,
+                     "tasks_per_level": r.tasks_per_level, "leaves_per_level": r.leaves_per_level,
+                     "area_quad": r.area_quad_str, "area_hex": float(got).hex()}
+        print("edges", name, r.tasks, r.leaves, r.levels, repr(got))
+    with open(os.path.join(OUT, "edges.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     if not shutil.which(MPIRUN) and not os.path.exists(MPIRUN):
         print("warning: no mpirun; reference stdout will not be recorded")
     O.build()
-    which = sys.argv[1:] or ["trees", "plugin", "libm_bits", "sin_bits", "batch", "deep"]
+    which = sys.argv[1:] or ["trees", "plugin", "libm_bits", "sin_bits", "batch", "deep", "edges"]
     for name in which:
         {"trees": trees, "plugin": plugin, "libm_bits": libm_bits, "sin_bits": sin_bits, "batch": batch,
-         "deep": deep}[name]()
+         "deep": deep, "edges": edges}[name]()
