@@ -362,6 +362,61 @@ int aq_integrate_batch_tol(aq_ctx *ctx, size_t n, const double *a, const double 
                            double *err_abs, double *err_signed,
                            double *eps_used, int32_t *rounds);
 
+/* ---- device-resident batch: device arrays in and out, ordered on a stream ---------------------------
+ * aq_integrate_batch_device is the _err batch (and, with both error outputs NULL, the plain and _params
+ * batch) for a caller whose bounds and parameter rows are already on the GPU and whose results stay there:
+ * every pointer of aq_device_io is DEVICE memory of the context's device. The call only ENQUEUES: it reads no
+ * bound on the host, copies nothing to or from the host and waits for no stream or event, whatever n (its
+ * only blocking work is the allocation of its device rings, by the first such call of a context -- and, for
+ * AQ_F_PARAM, of their theta part by the first such AQ_F_PARAM call; aq_ctx_device_bytes does not move before).
+ * Ordering. `stream` points to the caller's hipStream_t (the pointer's target may be the null stream): the
+ * context's stream first waits for everything enqueued on that stream so far, and before the call returns
+ * that stream has been made to wait for the last output write -- work the caller enqueues on it afterwards
+ * sees complete outputs, and may free or overwrite the inputs. stream == NULL: no caller's stream; the inputs
+ * must be complete when the call is made, and aq_synchronize or aq_device_batch_check orders the outputs.
+ * Results. The same trees, counts, areas and error sums as aq_integrate_batch_err gives for the same rows
+ * (the sums within the bound stated there), in input order; ERR launches (8 waves per workgroup) run iff
+ * err_abs or err_signed is non-NULL, plain launches otherwise. Any output may be NULL.
+ * Per-row status in place of an all-or-nothing AQ_EINVAL: a row outside the domain (the rule of AQ_EINVAL
+ * above, checked on the device by the same predicate the host calls use) gets status AQ_ROW_INVALID, area and
+ * error sums NaN and accepted = tasks = 0, and disturbs no other row (inside the launch it runs as the empty
+ * interval [0, 0], one task, which aq_cu_task_counters does count). A row whose slot carries error bits gets
+ * them in status, and the outputs the host batch would give for it: AQ_ROW_DEPTH on the rows whose own tree
+ * reached max_depth, AQ_ROW_TIMEOUT and AQ_ROW_OVERFLOW -- the launch's, which no row can be blamed for -- on
+ * every row of the chunk. Other rows get status 0.
+ * AQ_EINVAL from the host: a NULL ctx or io, NULL a or b with n > 0, a theta that does not go with the
+ * integrand (the rule of the _err calls), a bad eps, max_depth or integrand. n == 0 returns AQ_OK and enqueues
+ * nothing. Device pointers are NOT otherwise validated (a host pointer or a short array is undefined
+ * behaviour), and inputs that overlap outputs are undefined.
+ * aq_device_batch_check waits for the context's stream, stores in *invalid_rows (may be NULL) the number of
+ * AQ_ROW_INVALID rows since the last check, and returns AQ_EINVAL if there were any, else the code of the OR of
+ * the rows' error bits since the last check (AQ_ETIMEOUT, AQ_EOVERFLOW, AQ_EDEPTH), else AQ_OK; it then resets
+ * both. Before the first device batch of a context it reports 0 and AQ_OK.
+ * The rows run in chunks of up to aq_max_integrals_per_launch() (AQ_DEVBATCH_CHUNK=<n> in the environment,
+ * read per call and clamped to [1, that], sets a smaller chunk), each in size order (AQ_BATCH_SORT=0: input
+ * order); the next chunk is checked and sized on a side stream while one runs. The launches use slots
+ * 0 .. chunk-1 -- a chunk of fewer than 12 rows slots from 16384 -- and leave them clean; the call has
+ * device rings and events of its own, so the other calls of the context may follow it without waiting.
+ * Not covered: a device form of aq_integrate_batch_tol (it needs one host look per round by design), shards
+ * and aq_group, the frontier engine, the CLI. */
+#define AQ_ROW_TIMEOUT  1u   /* the slot error bits, as in a gathered row's 4th field ... */
+#define AQ_ROW_OVERFLOW 2u
+#define AQ_ROW_DEPTH    4u
+#define AQ_ROW_INVALID  8u   /* ... and: the row failed the domain check and was not integrated */
+typedef struct {
+    const double *a, *b;          /* DEVICE, [n] */
+    const double *theta;          /* DEVICE, [n * aq_param_count()] row-major; non-NULL exactly for AQ_F_PARAM */
+    double   *area;               /* DEVICE [n] or NULL */
+    uint64_t *accepted, *tasks;   /* DEVICE [n] or NULL */
+    double   *err_abs, *err_signed; /* DEVICE [n] or NULL; ERR launches run iff one of them is non-NULL */
+    uint32_t *status;             /* DEVICE [n] or NULL: 0, or AQ_ROW_* bits */
+    int32_t   max_depth;          /* as aq_problem.max_depth */
+    int32_t   reserved;
+} aq_device_io;
+int aq_integrate_batch_device(aq_ctx *ctx, size_t n, const aq_device_io *io, double eps, int integrand,
+                              void *const *stream);
+int aq_device_batch_check(aq_ctx *ctx, uint64_t *invalid_rows);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel on the context's
  * stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */

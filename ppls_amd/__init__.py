@@ -12,6 +12,7 @@ from .aquad import (  # noqa: F401
     USER,
     AquadError,
     Context,
+    DeviceBatch,
     Group,
     Problem,
     Result,
@@ -25,6 +26,6 @@ from .aquad import (  # noqa: F401
     user_integrand_name,
 )
 
-__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "Group", "Problem", "Result", "TolResult",
+__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "DeviceBatch", "Group", "Problem", "Result", "TolResult",
            "exact_round",
            "farmer", "format_reference", "integrate", "param_count", "param_integrand_name", "user_integrand_name"]

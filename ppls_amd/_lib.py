@@ -24,6 +24,7 @@ EXPORTS = (
     "aq_integrate_many_params_async", "aq_integrate_batch_params",
     "aq_err_extrapolate", "aq_integrate_err", "aq_integrate_many_err_async", "aq_fetch_err", "aq_integrate_batch_err",
     "aq_integrate_batch_tol",
+    "aq_integrate_batch_device", "aq_device_batch_check",
 )
 
 AQ_MAX_LEVELS = 128
@@ -55,6 +56,13 @@ class aq_err(ctypes.Structure):
 class aq_tol(ctypes.Structure):
     _fields_ = [("epsabs", ctypes.c_double), ("epsrel", ctypes.c_double), ("eps0", ctypes.c_double),
                 ("shrink", ctypes.c_double), ("max_rounds", ctypes.c_int32), ("max_depth", ctypes.c_int32)]
+
+
+class aq_device_io(ctypes.Structure):
+    """Device pointers (aquad.h aq_device_io): a, b, theta in; area, accepted, tasks, err_abs, err_signed, status out."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("a", "b", "theta", "area", "accepted", "tasks", "err_abs",
+                                                     "err_signed", "status")] + \
+               [("max_depth", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 _lib = None
@@ -142,6 +150,9 @@ def load(build_if_missing=True):
         "aq_integrate_batch_err": ([vp, ctypes.c_size_t, dp, dp, dp, c_dbl, c_int, dp, up, up, dp, dp], c_int),
         "aq_integrate_batch_tol": ([vp, ctypes.c_size_t, dp, dp, dp, c_int, ctypes.POINTER(aq_tol), dp, up, up, dp, dp,
                                     dp, ip], c_int),
+        "aq_integrate_batch_device": ([vp, ctypes.c_size_t, ctypes.POINTER(aq_device_io), c_dbl, c_int,
+                                       ctypes.POINTER(vp)], c_int),
+        "aq_device_batch_check": ([vp, up], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

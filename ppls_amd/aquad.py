@@ -7,6 +7,7 @@ Reference: /root/reference/aquadPartA.c
   - main()'s printout (:107-117)                   -> format_reference()
 Everything here calls the HIP engine through the C ABI (include/aquad.h). There is no CPU path.
 """
+import collections
 import ctypes
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -79,6 +80,13 @@ class TolResult(tuple):
         self = super().__new__(cls, arrays)
         self.converged = bool(converged)
         return self
+
+
+# Context.integrate_batch_device's result: torch CUDA tensors of n in input order -- area, err_abs, err_signed f64
+# (the two error sums None unless err=True); tasks, accepted int64 (the ABI's uint64_t bits; counts are below
+# 2^63); status int32: 0, or ROW_* bits.
+DeviceBatch = collections.namedtuple("DeviceBatch", "area tasks accepted err_abs err_signed status")
+ROW_TIMEOUT, ROW_OVERFLOW, ROW_DEPTH, ROW_INVALID = 1, 2, 4, 8   # aquad.h AQ_ROW_*
 
 
 def _check(rc, what):
@@ -438,6 +446,67 @@ class Context:
                                              integrand, _dp(area), _up(acc), _up(tasks), _dp(err_abs), _dp(err_signed)),
                "aq_integrate_batch_err")
         return area, tasks, acc, err_abs, err_signed
+
+    # -- device-resident batch: torch CUDA tensors in and out, ordered on the current stream ---
+    def integrate_batch_device(self, a, b, eps, integrand=COSH4, theta=None, err=False, max_depth=0,
+                               out=None) -> DeviceBatch:
+        """integrate_batch_err for bounds (and PARAM theta rows) that are already on the GPU, with the results left
+        there: a, b (n,) and theta (n, param_count()) are contiguous float64 CUDA tensors on the context's device
+        (anything else raises ValueError: nothing is moved or copied for the caller). Enqueues only, ordered on
+        torch's current stream: the call's work follows what that stream holds, and the stream is made to wait
+        for the outputs before the call returns -- the returned tensors are usable on it at once, the inputs may be
+        freed, no record_stream needed. err=True: ERR launches, err_abs and err_signed filled (else None).
+        A row outside the domain gets status ROW_INVALID, NaN area and zero counts instead of failing the call;
+        device_batch_check() reports them. out: a DeviceBatch (or 6-tuple) of tensors to write into."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def want(t, shape, dtype, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and
+                    tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+            return t
+
+        if not isinstance(a, torch.Tensor) or a.dim() != 1:
+            raise ValueError("a must be a 1-d torch tensor")
+        n = a.shape[0]
+        want(a, (n,), torch.float64, "a")
+        want(b, (n,), torch.float64, "b")
+        if (integrand == PARAM) != (theta is not None):
+            raise ValueError("theta goes with the PARAM integrand, and with it only")
+        if theta is not None:
+            want(theta, (n, param_count()), torch.float64, "theta")
+        kinds = (("area", torch.float64), ("tasks", torch.int64), ("accepted", torch.int64), ("err_abs", torch.float64),
+                 ("err_signed", torch.float64), ("status", torch.int32))
+        if out is None:
+            out = DeviceBatch(*(torch.empty(n, dtype=dt, device=dev) if err or not name.startswith("err_") else None
+                                for name, dt in kinds))
+        else:
+            out = DeviceBatch(*out)
+            for (name, dt), t in zip(kinds, out):
+                if name.startswith("err_") and not err:
+                    if t is not None:
+                        raise ValueError(f"out.{name} goes with err=True only")
+                else:
+                    want(t, (n,), dt, "out." + name)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        io = _lib.aq_device_io(ptr(a), ptr(b), ptr(theta), ptr(out.area), ptr(out.accepted), ptr(out.tasks),
+                               ptr(out.err_abs), ptr(out.err_signed), ptr(out.status), int(max_depth), 0)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(self.L.aq_integrate_batch_device(self._h, n, ctypes.byref(io), float(eps), integrand,
+                                                ctypes.byref(stream)), "aq_integrate_batch_device")
+        return out
+
+    def device_batch_check(self, raise_on_error=True) -> int:
+        """Waits for the context's stream; the number of ROW_INVALID rows of the device batches since the last
+        check. raise_on_error: AquadError with code AQ_EINVAL if there were any, else with the code of the rows'
+        error bits if a row had some. Resets both."""
+        n = ctypes.c_uint64(0)
+        rc = self.L.aq_device_batch_check(self._h, ctypes.byref(n))
+        if raise_on_error or rc == -2:   # (a HIP failure always raises)
+            _check(rc, "aq_device_batch_check")
+        return int(n.value)
+
 
     # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------
     def integrate_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12, integrand=COSH4,

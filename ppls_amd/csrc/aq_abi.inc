@@ -3,6 +3,7 @@
 // ================================================================================================
 #include "aq_host_args.h"   // the argument rules and the chunk schedule (no HIP: tests/test_host_args.py)
 #include "aq_batch_plan.h"  // the batch front end's pipeline: steps, streams, events (no HIP: tests/test_batch_plan.py)
+#include "aq_device_batch_plan.h"   // ... and the device-resident batch's (no HIP: tests/test_device_batch_plan.py)
 #include "aq_host_mem.h"    // owning device / pinned buffers, events, streams
 
 using namespace aq;
@@ -45,23 +46,8 @@ static_assert(HB_TIMEOUT == ERRB_TIMEOUT && HB_OVERFLOW == ERRB_OVERFLOW && HB_D
 
 bool integrand_ok(int f) { return f == AQ_F_COSH4 || f == AQ_F_SIN_RECIP || f == AQ_F_USER; }
 
-// The supported domain. The kernels compare DOUBLED areas (aq_device.h task_step_k), which are the
-// reference's own products (F(l)+F(r))*(r-l) before its '/2'; the sums l2 + r2 must stay finite
-// where the reference's halves do, so every |F| * width stays far below 2^1023: bounds within
-// 2^900, and for cosh^4 (F ~ e^{4|x|}/16, 16 F in the rounds) |x| <= 170. The persistent kernel's
-// rings hold HALVED endpoints (pair_step_halves), exact while every coordinate of the tree is 0 or
-// at least 2^-1021 in magnitude: nonzero bounds of at least 2^-900 keep the smallest coordinate a
-// 64-level tree can make (one cancelling midpoint, 2^-53 below the bounds' scale, then 64 halvings)
-// far above that.
-bool bounds_ok(int f, double a, double b) {
-    if (!(std::isfinite(a) && std::isfinite(b) && b >= a)) return false;
-    const double m = std::max(std::fabs(a), std::fabs(b));
-    if (m > 0x1p900) return false;
-    if ((a != 0.0 && std::fabs(a) < 0x1p-900) || (b != 0.0 && std::fabs(b) < 0x1p-900)) return false;
-    if (f == AQ_F_COSH4) return m <= 170.0;
-    if (f == AQ_F_USER) return user::domain_ok(a, b);
-    return true;
-}
+// (The supported domain -- bounds_ok, params_ok -- is aq_domain.h's: one predicate for these host checks and
+// the device-resident batch's check kernel.)
 
 int validate(const aq_problem* p) {
     if (!p) return AQ_EINVAL;
@@ -147,6 +133,61 @@ struct BatchRings {
                     cnt + 2 * EST_KEYS * (p ^ 1u), est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr,
                     par ? thsorted + p * R * NP : nullptr, err ? errrows + 2 * p * R : nullptr};
     }
+};
+
+// The device-resident batch's buffers (aq_integrate_batch_device): rings of its own, so that a call of the
+// host batch may follow one still in flight without waiting, and the events its plan names -- the context's,
+// reused from call to call, because the call returns while they are pending. The rings hold two chunks of
+// MAXK rows whatever the call's size: they are allocated once, by the context's first such call (theta and
+// its size-ordered copy by the first AQ_F_PARAM one), and no later call allocates, frees or waits. The layout
+// is BatchRings' (View), plus the check kernel's flag ring and what aq_device_batch_check reads.
+struct DevBatchRings {
+    static constexpr size_t R = (size_t)MAXK;
+    DevBuf<double2> bounds, sorted;   // [2][R]
+    DevBuf<unsigned> key;             // [R]
+    DevBuf<unsigned> perm, flag;      // [2][R]
+    DevBuf<unsigned> cnt;             // [2] x (EST_KEYS counts + EST_KEYS cursors)
+    DevBuf<double> est;               // [2]
+    DevBuf<double> theta, thsorted;   // [2][R][nparams]
+    DevBuf<DevBatchStat> stat;        // one: invalid rows and error bits since the last aq_device_batch_check
+    PinBuf<DevBatchStat> h_stat;      // its pinned copy
+    std::vector<Event> ev;            // by the plan's event numbers (grow-only)
+    explicit DevBatchRings(unsigned long long* bytes)
+        : bounds{bytes}, sorted{bytes}, key{bytes}, perm{bytes}, flag{bytes}, cnt{bytes}, est{bytes}, theta{bytes},
+          thsorted{bytes}, stat{bytes} {}
+
+    int ensure(bool par, size_t n_events) {
+        constexpr size_t NP = (size_t)param::nparams;
+        if (!stat) {
+            AQ_HIP(bounds.alloc(2 * R, false));
+            AQ_HIP(sorted.alloc(2 * R, false));
+            AQ_HIP(key.alloc(R, false));
+            AQ_HIP(perm.alloc(2 * R, false));
+            AQ_HIP(flag.alloc(2 * R, false));
+            AQ_HIP(cnt.alloc(4 * EST_KEYS, false));
+            AQ_HIP(est.alloc(2, false));
+            AQ_HIP(h_stat.alloc(1, true));
+            AQ_HIP(stat.alloc(1, true));
+        }
+        if (par && !theta) {
+            AQ_HIP(theta.alloc(NP * 2 * R, false));
+            AQ_HIP(thsorted.alloc(NP * 2 * R, false));
+        }
+        while (ev.size() < n_events) {
+            ev.emplace_back();
+            AQ_HIP(ev.back().create(hipEventDisableTiming));
+        }
+        return AQ_OK;
+    }
+    // chunk c's places in the rings, as BatchRings::at (no row rings: the gather writes the caller's arrays)
+    BatchRings::View at(size_t c, bool par) const {
+        constexpr size_t NP = (size_t)param::nparams;
+        const size_t p = c & 1u;
+        return BatchRings::View{nullptr, bounds + p * R, sorted + p * R, perm + p * R, cnt + 2 * EST_KEYS * p,
+                                cnt + 2 * EST_KEYS * (p ^ 1u), est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr,
+                                par ? thsorted + p * R * NP : nullptr, nullptr};
+    }
+    unsigned* flags(size_t c) const { return flag + (c & 1u) * R; }
 };
 
 // aq_integrate_batch_tol's buffers, for its largest block so far (grow-only up to MAXK rows): the live rows'
@@ -262,6 +303,7 @@ struct aq_ctx {
     bool slot_err[NSLOTS_ALL] = {};    // slot's last launch was an ERR launch (beside slot_hist)
     int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
     TolBufs tol{&dev_bytes};           // aq_integrate_batch_tol's buffers (allocated by its first call)
+    DevBatchRings devbatch{&dev_bytes};   // aq_integrate_batch_device's rings and events (allocated by its first call)
     // eval buffers (not counted)
     DevBuf<double> d_x, d_y;
     // host staging
@@ -553,14 +595,6 @@ int launch(aq_ctx* ctx, const LaunchArgs& g) {
         constexpr int FID = decltype(F)::value;
         return g.hist && !g.err ? launch_stream<FID, true>(ctx, g) : launch_stream<FID, false>(ctx, g);
     });
-}
-
-// One integral of the parametrised family: the engine's bounds rule, finite parameters, the plug-in's domain.
-bool params_ok(double a, double b, const double* th) {
-    if (!bounds_ok(AQ_F_PARAM, a, b)) return false;
-    for (int j = 0; j < param::nparams; ++j)
-        if (!std::isfinite(th[j])) return false;
-    return param::domain_ok(a, b, th);
 }
 
 // Per-CU counts of one GPU in hardware-slot order (the aq_result.tasks_per_cu row).
@@ -1514,6 +1548,31 @@ static int gather_clean(aq_ctx* ctx, int k, double* rows, double* errrows, const
     return AQ_OK;
 }
 
+// The size pre-pass of a sorted chunk of m rows, on stream s (the host batch's and the device-resident one's):
+// size classes from the estimates, the bounds (and theta, where the view has some) into size order; preset: the
+// scatter also sets the launch's job size from the estimates (AQ_F_* values are the kernels' FIDs)
+static int size_prepass(aq_ctx* ctx, int integrand, int m, double eps, const BatchRings::View& v, unsigned* key,
+                        bool preset, hipStream_t s) {
+    constexpr size_t NP = (size_t)param::nparams;
+    const unsigned blocks = (unsigned)((m + 255) / 256);
+    if (v.theta)
+        hipLaunchKernelGGL(k_batch_estimate_params, dim3(blocks), dim3(256), 0, s, v.bounds, (const double*)v.theta, m,
+                           eps, key, v.cnt, v.est, ctx->d_tab);
+    else
+        with_fid(integrand, [&](auto F) {
+            hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, v.bounds, m, eps, key,
+                               v.cnt, v.est, ctx->d_tab);
+        });
+    hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, s, v.bounds, key, m, v.cnt, v.cnt + EST_KEYS,
+                       v.sorted, v.perm, v.cnt_next, v.est, v.est_next, preset ? ctx->d_hint : nullptr,
+                       (unsigned)(ctx->grid * NW));
+    if (v.theta)
+        hipLaunchKernelGGL(k_batch_scatter_theta, dim3((unsigned)(((size_t)m * NP + 255) / 256)), dim3(256), 0, s,
+                           (const double*)v.theta, (const unsigned*)v.perm, m, (int)NP, v.thsorted);
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
 // a call's per-integral outputs (any may be null)
 struct RowsOut {
     double* area;
@@ -1596,29 +1655,8 @@ struct BatchCall {
         AQ_HIP(hipMemcpyAsync(v.bounds, B.h_bounds + off[c], sizeof(double2) * m, hipMemcpyHostToDevice, s));
         return AQ_OK;
     }
-    // size classes from the estimates, the bounds (and theta) into size order; preset: the scatter also sets
-    // the launch's job size from the estimates (AQ_F_* values are the kernels' FIDs)
     int pre(int c, hipStream_t s) {
-        const BatchRings::View v = B.at(c);
-        const int m = plan.chunks[c];
-        const unsigned blocks = (unsigned)((m + 255) / 256);
-        unsigned* const key = B.key;
-        if (plan.theta)
-            hipLaunchKernelGGL(k_batch_estimate_params, dim3(blocks), dim3(256), 0, s, v.bounds, (const double*)v.theta, m,
-                               eps, key, v.cnt, v.est, ctx->d_tab);
-        else
-            with_fid(integrand, [&](auto F) {
-                hipLaunchKernelGGL(k_batch_estimate<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, v.bounds, m, eps, key,
-                                   v.cnt, v.est, ctx->d_tab);
-            });
-        hipLaunchKernelGGL(k_batch_scatter, dim3(blocks), dim3(256), 0, s, v.bounds, key, m, v.cnt, v.cnt + EST_KEYS,
-                           v.sorted, v.perm, v.cnt_next, v.est, v.est_next, plan.preset[c] ? ctx->d_hint : nullptr,
-                           (unsigned)(ctx->grid * NW));
-        if (plan.theta)
-            hipLaunchKernelGGL(k_batch_scatter_theta, dim3((unsigned)(((size_t)m * NP + 255) / 256)), dim3(256), 0, s,
-                               (const double*)v.theta, (const unsigned*)v.perm, m, (int)NP, v.thsorted);
-        AQ_HIP(hipGetLastError());
-        return AQ_OK;
+        return size_prepass(ctx, integrand, plan.chunks[c], eps, B.at(c), B.key, plan.preset[c], s);
     }
     int launch_chunk(int c) {
         const BatchRings::View v = B.at(c);
@@ -1752,6 +1790,145 @@ int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double*
                            double* err_signed) {
     if (!ctx || !theta_ok(integrand, theta)) return AQ_EINVAL;
     return batch_run(ctx, n, a, b, theta, eps, integrand, area, accepted, tasks, true, err_abs, err_signed);
+}
+
+// ---- device-resident batch (aq_integrate_batch_device) ---------------------------------------------------
+// The caller's arrays are device memory and the call only enqueues: k_dev_check in place of the host's checks
+// and staging, the host batch's size pre-pass and launches, k_gather_reset_soa in place of the gathers, the
+// copy back and the unpacking. Which step runs where, behind what: device_batch_plan
+// (aq_device_batch_plan.h). DevBatchCall is one call's state and one function per step kind -- it orders
+// nothing.
+struct DevBatchCall {
+    aq_ctx* ctx;
+    const DevBatchRings& D;    // ctx->devbatch
+    const DevBatchPlan& plan;
+    std::vector<size_t> off;   // chunk c: rows [off[c], off[c + 1])
+    const aq_device_io& io;
+    double eps;
+    int integrand;
+    static constexpr size_t NP = (size_t)param::nparams;
+
+    int zero(hipStream_t s) {
+        AQ_HIP(hipMemsetAsync(D.cnt, 0, sizeof(unsigned) * 4 * EST_KEYS, s));
+        AQ_HIP(hipMemsetAsync(D.est, 0, sizeof(double) * 2, s));
+        return AQ_OK;
+    }
+    int check(int c, hipStream_t s) {
+        const BatchRings::View v = D.at(c, plan.theta);
+        const int m = plan.chunks[c];
+        const unsigned blocks = (unsigned)((m + 255) / 256);
+        const double *a = io.a + off[c], *b = io.b + off[c];
+        if (plan.theta)
+            hipLaunchKernelGGL(k_dev_check_params, dim3(blocks), dim3(256), 0, s, a, b, io.theta + off[c] * NP, m, v.bounds,
+                               v.theta, D.flags(c), D.stat.get());
+        else
+            with_fid(integrand, [&](auto F) {
+                hipLaunchKernelGGL(k_dev_check<decltype(F)::value>, dim3(blocks), dim3(256), 0, s, a, b, m, v.bounds,
+                                   D.flags(c), D.stat.get());
+            });
+        AQ_HIP(hipGetLastError());
+        return AQ_OK;
+    }
+    int pre(int c, hipStream_t s) {
+        return size_prepass(ctx, integrand, plan.chunks[c], eps, D.at(c, plan.theta), D.key, plan.preset[c], s);
+    }
+    // (no bounds on the host: plan.first_slot keeps every chunk off the per-CU instance, which takes them as
+    // kernel arguments)
+    int launch_chunk(int c) {
+        const BatchRings::View v = D.at(c, plan.theta);
+        LaunchArgs g;   // (no histograms: hist stays false)
+        g.integrand = integrand;
+        g.k = plan.chunks[c];
+        g.eps = eps;
+        g.max_depth = io.max_depth;
+        g.first_slot = plan.first_slot[c];
+        g.dev_bounds = plan.sorted[c] ? v.sorted : v.bounds;
+        g.dev_theta = plan.sorted[c] ? v.thsorted : v.theta;
+        g.err = plan.err;
+        g.heap = true;
+        ctx->hint.preset = plan.preset[c];
+        const int rc = launch(ctx, g);
+        ctx->hint.preset = false;
+        return rc;
+    }
+    // (the kernel returns the slots and their error sums to zero, as gather_clean's two do: they count as clean)
+    int gather(int c) {
+        const BatchRings::View v = D.at(c, plan.theta);
+        const int k = plan.chunks[c], first = plan.first_slot[c];
+        auto at = [&](auto* p) { return p ? p + off[c] : p; };
+        const SoaOut out{at(io.area), (unsigned long long*)at(io.accepted), (unsigned long long*)at(io.tasks),
+                         at(io.err_abs), at(io.err_signed), at(io.status)};
+        hipLaunchKernelGGL(k_gather_reset_soa, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl.get(),
+                           (const unsigned long long*)ctx->d_parts, ctx->grid, first, k,
+                           (const unsigned*)(plan.sorted[c] ? v.perm : nullptr), plan.err ? ctx->d_err.get() : nullptr,
+                           (const unsigned*)D.flags(c), io.max_depth ? io.max_depth : AQ_DEFAULT_MAX_DEPTH, out,
+                           D.stat.get());
+        AQ_HIP(hipGetLastError());
+        if (plan.err) memset(ctx->err_dirty + first, 0, (size_t)k);
+        memset(ctx->dirty + first, 0, (size_t)k);
+        memset(ctx->parts_dirty + first, 0, (size_t)k);
+        return AQ_OK;
+    }
+};
+
+int aq_integrate_batch_device(aq_ctx* ctx, size_t n, const aq_device_io* io, double eps, int integrand,
+                              void* const* stream) {
+    if (!ctx || !io || (n && (!io->a || !io->b))) return AQ_EINVAL;
+    if (!theta_ok(integrand, io->theta)) return AQ_EINVAL;
+    if (!(eps >= 0.0) || io->max_depth < 0 || io->max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    const bool par = integrand == AQ_F_PARAM, err = io->err_abs || io->err_signed;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const std::vector<int> chunks = device_batch_chunks(n, device_batch_chunk_rows(env_int("AQ_DEVBATCH_CHUNK", MAXK)));
+    const bool sort = env_int("AQ_BATCH_SORT", 1) != 0;
+    // (preset while the workload is fresh: no measured hint for this integrand and tolerance -- batch_run's rule)
+    const bool fresh = ctx->gsplit_env <= 0 && !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps &&
+                                                 ctx->hint.nshards == 1);
+    const DevBatchPlan plan = device_batch_plan(chunks, sort, par, err, fresh, stream != nullptr);
+    int rc = ctx->devbatch.ensure(par, (size_t)plan.n_events());
+    if (rc) return rc;
+    if (err && (rc = ensure_err(ctx))) return rc;
+    if (!ctx->s_pre) AQ_HIP(ctx->s_pre.create());
+    const hipStream_t streams[] = {ctx->stream, ctx->s_pre, stream ? (hipStream_t)*stream : nullptr};   // by DStream
+    const std::vector<Event>& ev = ctx->devbatch.ev;
+    DevBatchCall call{ctx, ctx->devbatch, plan, std::vector<size_t>(chunks.size() + 1, 0), *io, eps, integrand};
+    for (size_t c = 0; c < chunks.size(); ++c) call.off[c + 1] = call.off[c] + (size_t)chunks[c];
+    // (a failed step ends the call: what it enqueued so far runs out on its own, and waits for no event that
+    // is never recorded)
+    for (const DevBatchStep& s : plan.steps) {
+        const hipStream_t st = streams[(int)s.stream];
+        for (int w : s.wait)
+            if (w >= 0) AQ_HIP(hipStreamWaitEvent(st, ev[w], 0));
+        switch (s.kind) {
+            case DKind::JOIN_IN: case DKind::START: case DKind::FENCE: case DKind::JOIN_OUT: break;   // waits and records
+            case DKind::ZERO: rc = call.zero(st); break;
+            case DKind::CHECK: rc = call.check(s.chunk, st); break;
+            case DKind::PRE: rc = call.pre(s.chunk, st); break;
+            case DKind::LAUNCH: rc = call.launch_chunk(s.chunk); break;
+            case DKind::GATHER: rc = call.gather(s.chunk); break;
+        }
+        if (rc) return rc;
+        if (s.record >= 0) AQ_HIP(hipEventRecord(ev[s.record], st));
+    }
+    return AQ_OK;
+}
+
+int aq_device_batch_check(aq_ctx* ctx, uint64_t* invalid_rows) {
+    if (!ctx) return AQ_EINVAL;
+    if (invalid_rows) *invalid_rows = 0;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const DevBatchRings& D = ctx->devbatch;
+    if (!D.stat) {   // no device batch yet
+        AQ_HIP(hipStreamSynchronize(ctx->stream));
+        return AQ_OK;
+    }
+    // (the pinned-word read of read_slot: an asynchronous copy into pinned memory, then the stream)
+    AQ_HIP(hipMemcpyAsync(D.h_stat, D.stat, sizeof(DevBatchStat), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemsetAsync(D.stat, 0, sizeof(DevBatchStat), ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    const DevBatchStat st = *D.h_stat;
+    if (invalid_rows) *invalid_rows = st.invalid;
+    return st.invalid ? AQ_EINVAL : err_from_bits(st.errbits);
 }
 
 // ---- tolerance-driven batch (aq_integrate_batch_tol) -----------------------------------------------------

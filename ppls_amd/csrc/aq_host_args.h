@@ -1,6 +1,6 @@
 // aq_host_args.h -- the C ABI's argument rules that need no device: the range rules every launch entry point
 // shares, the slot-range rule of the gathers, the error code of a slot's error bits, and the batch front
-// end's chunk schedule. aq_abi.inc adds the integrands' domain predicates (they need the plug-ins).
+// end's chunk schedule. aq_domain.h holds the integrands' domain predicates (they need the plug-ins).
 //
 // Plain host C++17, no HIP: the CPU tests build it with g++ (tests/test_host_args.py).
 #pragma once

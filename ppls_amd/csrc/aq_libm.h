@@ -320,9 +320,14 @@ enum : int { F_COSH4 = 0, F_SIN_RECIP = 1, F_USER = 2, F_PARAM = 3 };
 //   constexpr const char* name;                                  -- reported by aq_user_integrand_name()
 //   __device__ double F(double x, const aq::ExpEntry* tab);      -- the macro body (tab: LDS exp table
 //                                                                   for aq::exp_glibc_any / cosh_glibc)
-//   inline bool domain_ok(double a, double b);                   -- host check of [a, b]
+//   AQ_DOMAIN_HD inline bool domain_ok(double a, double b);      -- check of [a, b], on the host (every entry
+//                                                                   point's argument check) AND on the device
+//                                                                   (k_dev_check, the device-resident batch):
+//                                                                   AQ_DOMAIN_HD is __host__ __device__ under
+//                                                                   hipcc (aq_domain_hd.h), so plain arithmetic only
 // and is compiled into every kernel as integrand id 2. Plug-in trees use the reference's own area
 // expressions literally (no doubled-area rescaling), so they are bit-exact for any finite F.
+#include "aq_domain_hd.h"
 #ifndef AQ_USER_F_HEADER
 #define AQ_USER_F_HEADER "plugins/aq_user_gauss.h"
 #endif
@@ -334,7 +339,8 @@ enum : int { F_COSH4 = 0, F_SIN_RECIP = 1, F_USER = 2, F_PARAM = 3 };
 //   constexpr const char* name;                                  -- reported by aq_param_integrand_name()
 //   constexpr int nparams;                                       -- 1 .. AQ_MAX_PARAMS (aq_param_count())
 //   __device__ double F(double x, const double (&th)[nparams], const aq::ExpEntry* tab);
-//   inline bool domain_ok(double a, double b, const double* th); -- host check of one integral
+//   AQ_DOMAIN_HD inline bool domain_ok(double a, double b, const double* th); -- check of one integral, host
+//                                                                   and device like aq::user::domain_ok
 // and is compiled in as integrand id 3. It runs through the persistent kernel and the batch front end
 // only (aq_integrate_params, aq_integrate_many_params_async, aq_integrate_batch_params,
 // aq_eval_integrand_params): the level-synchronous path, the frontier engine and aq_integrate_group

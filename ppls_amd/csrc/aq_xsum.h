@@ -79,10 +79,12 @@ AQ_HD void xs_add_xs(XSum& a, const XSum& b) {
 // 2^e0: the whole accumulator (N = n = XS_LIMBS, e0 = XS_E0), or a window of it that holds every
 // nonzero limb (the batch gather reads only a slot's touched limbs: SlotSums' limb window) -- the
 // value, and so its rounding, does not depend on the zero limbs around the window.
-template <int N>
-AQ_HD double xs_round_span(const long long* limb, int n, int e0) {
+// (dg: room for n + 2 digits -- an array of the caller's, or a pointer to where a kernel keeps them:
+// k_gather_reset_soa has the whole accumulator's in LDS, where a private array of that size would live in
+// scratch memory)
+template <typename Digits>
+AQ_HD double xs_round_digits(Digits& dg, const long long* limb, int n, int e0) {
     // carry-propagate into base-2^32 digits of the two's complement value
-    uint32_t dg[N + 2];
     long long carry = 0;
     for (int i = 0; i < n; ++i) {
         // v = limb + carry cannot overflow: |limb| < 2^63 - 2^33 by the addition budget, |carry| < 2^32
@@ -143,6 +145,11 @@ AQ_HD double xs_round_span(const long long* limb, int n, int e0) {
     };
     r = r * pow2(ex1) * pow2(ex2);
     return neg ? -r : r;
+}
+template <int N>
+AQ_HD double xs_round_span(const long long* limb, int n, int e0) {
+    uint32_t dg[N + 2];
+    return xs_round_digits(dg, limb, n, e0);
 }
 
 AQ_HD double xs_round(const XSum& a) { return xs_round_span<XS_LIMBS>(a.limb, XS_LIMBS, XS_E0); }

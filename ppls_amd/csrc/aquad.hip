@@ -26,6 +26,7 @@
 #include "aquad.h"
 #include "aq_exp_table.h"
 #include "aq_libm.h"
+#include "aq_domain.h"
 #include "aq_device.h"
 #include "aq_stream.h"
 #include "aq_launch_plan.h"
@@ -724,6 +725,145 @@ __global__ __launch_bounds__(64) void k_gather_err(double* __restrict__ err, int
     o[0] = e[0];
     o[1] = e[1];
     e[0] = e[1] = 0.0;
+}
+
+// ---- the device-resident batch (aq_integrate_batch_device) ------------------------------------------------
+// Its two ends, in place of the host batch's staging threads and unpacking threads: k_dev_check before a
+// chunk's size pre-pass and launch, k_gather_reset_soa behind the launch. Both read and write the CALLER's
+// device arrays at the chunk's offset (the host passes the offset pointers); the schedule is
+// aq_device_batch_plan.h's.
+constexpr unsigned ROW_INVALID = AQ_ROW_INVALID;
+static_assert(AQ_ROW_TIMEOUT == ERRB_TIMEOUT && AQ_ROW_OVERFLOW == ERRB_OVERFLOW && AQ_ROW_DEPTH == ERRB_DEPTH &&
+                  (AQ_ROW_INVALID & (ERRB_TIMEOUT | ERRB_OVERFLOW | ERRB_DEPTH)) == 0,
+              "aquad.h's row status bits are the slots' error bits, and one more");
+// What aq_device_batch_check reads and zeroes: rows that failed the check, the OR of the rows' error bits.
+struct DevBatchStat {
+    unsigned long long invalid;
+    unsigned errbits, pad;
+};
+
+// One row per thread: the domain predicate the host's checks use (aq_domain.h), the row into the chunk's
+// bounds ring (theta ring) -- a row outside the domain as the empty interval [0, 0] with a zeroed theta row,
+// which every integrand accepts at its root (width 0: the difference is 0 or NaN, never > eps) and the size
+// pre-pass puts in its smallest class (estimate 0) -- and its flag. The invalid rows are counted per wave
+// (ballot) and added by the wave's first lane: one atomic per wave that saw one, none otherwise.
+template <int FID>
+__device__ __forceinline__ void dev_check(const double* __restrict__ a, const double* __restrict__ b,
+                                          const double* __restrict__ theta, int n, double2* __restrict__ bounds,
+                                          double* __restrict__ th_out, unsigned* __restrict__ flag,
+                                          DevBatchStat* __restrict__ stat) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    bool bad = false;
+    if (i < n) {
+        double x = a[i], y = b[i];
+        if constexpr (FID == F_PARAM) {
+            constexpr int NP = param::nparams;
+            double th[NP];
+#pragma unroll
+            for (int j = 0; j < NP; ++j) th[j] = theta[(size_t)i * NP + j];
+            bad = !params_ok(x, y, th);
+#pragma unroll
+            for (int j = 0; j < NP; ++j) th_out[(size_t)i * NP + j] = bad ? 0.0 : th[j];
+        } else {
+            bad = !bounds_ok(FID, x, y);
+        }
+        if (bad) x = y = 0.0;
+        bounds[i] = make_double2(x, y);
+        flag[i] = bad ? ROW_INVALID : 0u;
+    }
+    const unsigned long long m = __ballot(bad);
+    if (m != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        atomicAdd(&stat->invalid, (unsigned long long)__popcll(m));
+}
+template <int FID>
+__global__ __launch_bounds__(256) void k_dev_check(const double* __restrict__ a, const double* __restrict__ b, int n,
+                                                   double2* __restrict__ bounds, unsigned* __restrict__ flag,
+                                                   DevBatchStat* __restrict__ stat) {
+    static_assert(FID != F_PARAM, "the parametrised family's check takes theta (k_dev_check_params)");
+    dev_check<FID>(a, b, nullptr, n, bounds, nullptr, flag, stat);
+}
+__global__ __launch_bounds__(256) void k_dev_check_params(const double* __restrict__ a, const double* __restrict__ b,
+                                                          const double* __restrict__ theta, int n,
+                                                          double2* __restrict__ bounds, double* __restrict__ th_out,
+                                                          unsigned* __restrict__ flag, DevBatchStat* __restrict__ stat) {
+    dev_check<F_PARAM>(a, b, theta, n, bounds, th_out, flag, stat);
+}
+
+// k_gather_reset and k_gather_err in one, for the device-resident batch: slot first + i's results (integral
+// perm[i]'s, or i's) straight into the caller's typed arrays, any of which may be null -- the area, the counts
+// through the same f64 the host batch's rows carry them in (unpack_rows: exact below 2^53), the error sums
+// (err: the slots' sums behind an ERR launch, else null), status = the slot's error bits | the check's flag --
+// and the slot (and its sums) back to zero. k_stream ORs a wave's error bits into every slot of its launch; the
+// depth bit is kept only on the rows whose own tree reached the launch's max_depth (levels, which the slot does
+// count per integral), so a shallow row beside a capped one reports 0 -- a stall or an overflow cannot be
+// attributed and stays on every row of the chunk. A row the check flagged gets a NaN area and sums and zero counts
+// (its slot ran the empty interval). The chunk's error bits are OR-ed into the context's word, one atomic per
+// wave that saw one.
+struct SoaOut {
+    double* area;
+    unsigned long long *accepted, *tasks;
+    double *err_abs, *err_signed;
+    unsigned* status;
+};
+__global__ __launch_bounds__(64) void k_gather_reset_soa(Ctl* __restrict__ ctls, const unsigned long long* __restrict__ parts,
+                                                         int grid, int first, int n, const unsigned* __restrict__ perm,
+                                                         double* __restrict__ err, const unsigned* __restrict__ flag,
+                                                         int max_depth, SoaOut out, DevBatchStat* __restrict__ stat) {
+    // the digits of a whole accumulator (a window wider than GATHER_WIN limbs: rare), one lane at a time
+    __shared__ uint32_t s_dg[XS_LIMBS + 2];
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int slot = first + min(i, n - 1);
+    Ctl& c = ctls[slot];
+    SlotSums sm{};
+    int lo = 0, hi = 0;
+    if (i < n) {
+        sm = c.sums;
+        lo = sm.win_hi ? (int)~sm.win_lo_not : 0;
+        hi = sm.win_hi ? min((int)sm.win_hi, XS_LIMBS) : 0;
+    }
+    double area = 0.0;
+    for (unsigned long long wide = __ballot(hi - lo > GATHER_WIN); wide != 0ull; wide &= wide - 1ull) {
+        if ((int)threadIdx.x == __builtin_ctzll(wide)) {
+            uint32_t* const dg = s_dg;
+            area = xs_round_digits(dg, c.area.limb, XS_LIMBS, XS_E0);
+            for (int j = 0; j < XS_LIMBS; ++j) c.area.limb[j] = 0ll;
+        }
+    }
+    unsigned bits = 0u;
+    if (i < n) {
+        const Counts k = slot_counts(sm, parts + 2 * parts_row(slot) * grid, grid);
+        if (hi - lo <= GATHER_WIN) {
+            long long w[GATHER_WIN];
+#pragma unroll
+            for (int j = 0; j < GATHER_WIN; ++j) w[j] = lo + j < hi ? c.area.limb[lo + j] : 0ll;
+            area = xs_round_span<GATHER_WIN>(w, hi - lo, XS_E0 + 32 * lo);
+#pragma unroll
+            for (int j = 0; j < GATHER_WIN; ++j)
+                if (lo + j < hi) c.area.limb[lo + j] = 0ll;
+        }
+        c.sums = SlotSums{};
+        double ea = 0.0, es = 0.0;
+        if (err) {
+            double* e = err + 2 * (size_t)slot;
+            ea = e[0], es = e[1];
+            e[0] = e[1] = 0.0;
+        }
+        const size_t r = perm ? perm[i] : (unsigned)i;
+        const bool bad = flag[r] != 0u;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        bits = sm.error & (k.levels >= (unsigned)max_depth ? ~0u : ~(unsigned)ERRB_DEPTH);
+        if (out.area) out.area[r] = bad ? nan : area;
+        if (out.tasks) out.tasks[r] = bad ? 0ull : (unsigned long long)(double)k.tasks;
+        if (out.accepted) out.accepted[r] = bad ? 0ull : (unsigned long long)(double)k.leaves;
+        if (out.err_abs) out.err_abs[r] = bad ? nan : ea;
+        if (out.err_signed) out.err_signed[r] = bad ? nan : es;
+        if (out.status) out.status[r] = bits | flag[r];
+    }
+    unsigned any = 0u;
+#pragma unroll
+    for (unsigned bit = 1u; bit <= ERRB_DEPTH; bit <<= 1)
+        if (__ballot((bits & bit) != 0u) != 0ull) any |= bit;
+    if (any && threadIdx.x == 0) atomicOr(&stat->errbits, any);
 }
 
 // ---- aq_integrate_batch_tol: between two rounds' launches -----------------------------------------------

@@ -28,8 +28,10 @@ __device__ __forceinline__ double F(double x, const double (&th)[nparams], const
 }
 
 // Finite bounds and parameters within +-1e150 (t * t may overflow to inf: exp(-inf) = 0, never a NaN),
-// and a non-zero inverse scale. F is in [0, 1], so no area can overflow.
-inline bool domain_ok(double a, double b, const double* th) {
+// and a non-zero inverse scale. F is in [0, 1], so no area can overflow. AQ_DOMAIN_HD (aq_domain_hd.h): the
+// host's argument checks and the device-resident batch's check kernel both call it, so it is plain arithmetic
+// on its arguments -- no host-only library call, no global.
+AQ_DOMAIN_HD inline bool domain_ok(double a, double b, const double* th) {
     return a >= -1e150 && b <= 1e150 && th[0] >= -1e150 && th[0] <= 1e150 && th[1] >= -1e150 && th[1] <= 1e150 &&
            th[1] != 0.0;
 }

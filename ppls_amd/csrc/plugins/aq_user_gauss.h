@@ -24,8 +24,9 @@ __device__ __forceinline__ double F(double x, const ExpEntry* __restrict__ tab) 
 }
 
 // Any finite interval: exp(-x*x) is in [0, 1] (underflowing to 0 beyond |x| ~ 27.3), so no area
-// can overflow.
-inline bool domain_ok(double a, double b) { return a >= -1e150 && b <= 1e150; }
+// can overflow. AQ_DOMAIN_HD (aq_domain_hd.h): the host's argument checks and the device-resident batch's check
+// kernel both call it, so it is plain arithmetic on its arguments -- no host-only library call, no global.
+AQ_DOMAIN_HD inline bool domain_ok(double a, double b) { return a >= -1e150 && b <= 1e150; }
 
 }  // namespace user
 }  // namespace aq
