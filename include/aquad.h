@@ -417,6 +417,51 @@ int aq_integrate_batch_device(aq_ctx *ctx, size_t n, const aq_device_io *io, dou
                               void *const *stream);
 int aq_device_batch_check(aq_ctx *ctx, uint64_t *invalid_rows);
 
+/* ---- the accepted mesh: the tree's leaves in x order, and the running integral ----------------------
+ * aq_integrate_mesh builds the tree aq_frontier_integrate(ctx, p, frontier_cap, sync_every, ...) builds -- res is
+ * filled exactly as that call fills it -- and keeps what that call throws away: the partition of [a, b] into
+ * accepted subintervals. The call blocks. Every pointer of aq_mesh_io is DEVICE memory of the context's device.
+ * Nodes. An accepted task [l, r] with mid = (l + r) / 2 (aquadPartA.c:187) contributes the panels [l, mid] and
+ * [mid, r]; the nodes are all leaf bounds and midpoints in increasing order, m + 1 = 2 * accepted + 1 of them:
+ * x[2j] = l_j, x[2j+1] = mid_j, x[m] = b. f holds the very values the task steps computed (F(l), F(mid), F(r):
+ * nothing is evaluated again), level[k] the depth of the accepted task that owns panel [x_k, x_k+1].
+ * Running integral. With P_j = Σ_{i<j} (larea_i + rarea_i), each term the reference's own double (:189-190,
+ * :199): cum[2j] is P_j and cum[2j+1] is P_j + larea_j, each rounded to double once; cum[0] = 0 and cum[m] =
+ * P_accepted. The prefix is carried in double-double, its error <= accepted * 2^-100 * Σ|larea_i + rarea_i|, so
+ * every cum value is the correctly rounded exact prefix or its neighbour; cum[m] and res->area are two roundings
+ * of the same sum.
+ * Determinism. For given inputs x, f, cum and level are bit-identical from run to run and for every sync_every
+ * (the leaves leave the level kernels in schedule order, are sorted by their unique left bounds, and the scan's
+ * tree depends on the leaf count alone).
+ * *n_nodes receives 2 * accepted + 1. If that exceeds cap_nodes the tree is still walked to its end -- leaves
+ * past the capacity are counted, not stored -- res and *n_nodes are written, the return is AQ_EOVERFLOW and the
+ * arrays are unspecified: retry with the size reported. AQ_EOVERFLOW from the frontier capacity and AQ_EDEPTH
+ * are aq_frontier_integrate's; the mesh would have gaps, so the arrays are unspecified and *n_nodes = 0.
+ * AQ_EINVAL: a NULL ctx, p, io, n_nodes, x, f or cum; cap_nodes < 3 or > 2^31; the argument errors of
+ * aq_frontier_integrate; AQ_F_PARAM (the frontier engine takes no theta).
+ * Device memory: leaf records (48 bytes per leaf of cap_nodes / 2), sort keys, indices and scratch, and scan
+ * partials are context-owned, allocated by the first mesh call, grown on demand and freed with the context;
+ * aq_ctx_device_bytes does not move before that first call.
+ * aq_mesh_eval gives the integral from x_0 to each q of d_q[nq] from a mesh (device arrays of n_nodes): for
+ * x_0 <= q <= x_m, with k the largest index <= m - 1 such that x_k <= q, one IEEE operation each:
+ *   h = q - x_k;  w = x_k+1 - x_k;  fq = f_k + (f_k+1 - f_k) * (h / w);  out = cum_k + (f_k + fq) * h / 2
+ * -- the trapezoid rule on the partial panel: continuous across nodes up to rounding, monotone where F >= 0,
+ * equal to cum_k at every node x_k, k < m (at x_m: cum_m-1 plus the last panel's trapezoid), its error on a full leaf the leaf's accepted |d| <= EPSILON. A q outside
+ * [x_0, x_m], or NaN, gives NaN. The call only enqueues on the context's stream and reads nothing on the host
+ * (aq_synchronize orders the output). AQ_EINVAL: a NULL ctx, a NULL array with nq > 0, n_nodes < 3.
+ * Not covered: meshes from the persistent kernel (aq_integrate*, shards, aq_group, the batches, the
+ * tolerance-driven batch), AQ_F_PARAM, several meshes per call, host-memory outputs (callers copy), the CLI. */
+typedef struct {
+    double  *x;      /* DEVICE [cap_nodes]: x_0 = a < x_1 < ... < x_m = b, m = 2 * accepted */
+    double  *f;      /* DEVICE [cap_nodes]: F(x_k), the values the tree evaluated */
+    double  *cum;    /* DEVICE [cap_nodes]: running integral, cum_0 = 0 */
+    uint8_t *level;  /* DEVICE [cap_nodes - 1] or NULL: depth of the accepted task that owns panel k */
+} aq_mesh_io;
+int aq_integrate_mesh(aq_ctx *ctx, const aq_problem *p, uint32_t frontier_cap, int sync_every,
+                      uint64_t cap_nodes, const aq_mesh_io *io, aq_result *res, uint64_t *n_nodes);
+int aq_mesh_eval(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const double *d_f, const double *d_cum,
+                 size_t nq, const double *d_q, double *d_out);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel on the context's
  * stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */

@@ -25,6 +25,7 @@ EXPORTS = (
     "aq_err_extrapolate", "aq_integrate_err", "aq_integrate_many_err_async", "aq_fetch_err", "aq_integrate_batch_err",
     "aq_integrate_batch_tol",
     "aq_integrate_batch_device", "aq_device_batch_check",
+    "aq_integrate_mesh", "aq_mesh_eval",
 )
 
 AQ_MAX_LEVELS = 128
@@ -63,6 +64,11 @@ class aq_device_io(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ("a", "b", "theta", "area", "accepted", "tasks", "err_abs",
                                                      "err_signed", "status")] + \
                [("max_depth", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class aq_mesh_io(ctypes.Structure):
+    """Device pointers (aquad.h aq_mesh_io): the mesh's x, f, cum [cap_nodes] and level [cap_nodes - 1] (or NULL)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("x", "f", "cum", "level")]
 
 
 _lib = None
@@ -153,6 +159,8 @@ def load(build_if_missing=True):
         "aq_integrate_batch_device": ([vp, ctypes.c_size_t, ctypes.POINTER(aq_device_io), c_dbl, c_int,
                                        ctypes.POINTER(vp)], c_int),
         "aq_device_batch_check": ([vp, up], c_int),
+        "aq_integrate_mesh": ([vp, P, ctypes.c_uint32, c_int, ctypes.c_uint64, ctypes.POINTER(aq_mesh_io), R, up], c_int),
+        "aq_mesh_eval": ([vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

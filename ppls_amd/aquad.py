@@ -507,6 +507,66 @@ class Context:
             _check(rc, "aq_device_batch_check")
         return int(n.value)
 
+    # -- the accepted mesh: the tree's leaves in x order, and the running integral ------------
+    def integrate_mesh(self, problem: Problem, cap_nodes=None, frontier_cap=1 << 22, sync_every=4):
+        """The adaptive mesh of one integral (aq_integrate_mesh): (Result, x, f, cum, level), the four arrays torch
+        CUDA tensors on the context's device trimmed to n_nodes = 2 * accepted + 1 (level: n_nodes - 1, uint8) --
+        the nodes in increasing order, F there as the tree evaluated it, the running integral (cum[0] = 0, cum[-1]
+        the area) and the depth of the accepted task that owns each panel. Blocks. cap_nodes=None sizes the arrays
+        from a first integrate() call's accepted count. A cap_nodes that is too small raises AquadError (code
+        AQ_EOVERFLOW) whose n_nodes attribute is the size to retry with."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if cap_nodes is None:
+            cap_nodes = 2 * self.integrate(problem).accepted + 1
+        cap_nodes = int(cap_nodes)
+        if cap_nodes < 3:
+            raise ValueError("cap_nodes must be at least 3")
+        x, f, cum = (torch.empty(cap_nodes, dtype=torch.float64, device=dev) for _ in range(3))
+        level = torch.empty(cap_nodes - 1, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # the allocator's blocks are free of torch's own work
+        io = _lib.aq_mesh_io(x.data_ptr(), f.data_ptr(), cum.data_ptr(), level.data_ptr())
+        r = _lib.aq_result()
+        n = ctypes.c_uint64(0)
+        rc = self.L.aq_integrate_mesh(self._h, ctypes.byref(problem.c()), int(frontier_cap), int(sync_every), cap_nodes,
+                                      ctypes.byref(io), ctypes.byref(r), ctypes.byref(n))
+        if rc == -4 and n.value:   # AQ_EOVERFLOW of cap_nodes (the frontier's leaves n_nodes at 0)
+            e = AquadError(f"aq_integrate_mesh: the mesh has {n.value} nodes, cap_nodes is {cap_nodes} (code {rc})", rc)
+            e.n_nodes = int(n.value)
+            raise e
+        _check(rc, "aq_integrate_mesh")
+        m = int(n.value)
+        return self._result(r), x[:m], f[:m], cum[:m], level[:m - 1]
+
+    def mesh_eval(self, x, f, cum, q):
+        """The integral from x[0] to every q on a mesh of integrate_mesh (aq_mesh_eval: the trapezoid rule on the
+        partial panel; NaN for a q outside [x[0], x[-1]] or NaN). x, f, cum (n_nodes,) and q (any shape) are
+        contiguous float64 CUDA tensors on the context's device (anything else raises ValueError); returns a
+        tensor of q's shape. Waits for torch's current stream before the call and for the result after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def want(t, what, shape=None):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float64 and
+                    t.is_contiguous() and (shape is None or tuple(t.shape) == shape)):
+                raise ValueError(f"{what} must be a contiguous float64 tensor on {dev}" +
+                                 (f" of shape {shape}" if shape else ""))
+            return t
+
+        if not isinstance(x, torch.Tensor) or x.dim() != 1:
+            raise ValueError("x must be a 1-d torch tensor")
+        n = x.shape[0]
+        want(x, "x")
+        want(f, "f", (n,))
+        want(cum, "cum", (n,))
+        want(q, "q")
+        out = torch.empty_like(q)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.L.aq_mesh_eval(self._h, n, x.data_ptr(), f.data_ptr(), cum.data_ptr(), q.numel(), q.data_ptr(),
+                                   out.data_ptr()), "aq_mesh_eval")
+        self.synchronize()
+        return out
+
 
     # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------
     def integrate_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12, integrand=COSH4,

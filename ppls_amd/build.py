@@ -29,7 +29,8 @@ HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off",
              "-mllvm", "-amdgpu-atomic-optimizer-strategy=None",
              "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
-SOURCES = [os.path.join(CSRC, "aquad.hip")]
+# aq_mesh_sort.hip: the accepted mesh's sort, the one user of rocPRIM (header-only, under the ROCm install)
+SOURCES = [os.path.join(CSRC, "aquad.hip"), os.path.join(CSRC, "aq_mesh_sort.hip")]
 # AQ_F_USER plug-in header (the reference's F(arg) macro, aquadPartA.c:46): the default Gaussian,
 # or any header named by PPLS_AMD_USER_F (see csrc/plugins/aq_user_gauss.h for the interface)
 USER_F = os.path.abspath(os.environ.get("PPLS_AMD_USER_F") or os.path.join(CSRC, "plugins", "aq_user_gauss.h"))

@@ -291,6 +291,13 @@ struct aq_ctx {
     bool defer_fold = false;           // aq_level_defer_fold: level steps leave their rows for one later fold
     int lp_pending = 0;                // level-step rows written and not yet folded
     double* lp_acc = nullptr;          // ... into this accumulator (the caller's)
+    // the accepted mesh (aq_integrate_mesh), allocated by its first call and grown on demand
+    DevBuf<Leaf> d_leaf{&dev_bytes};                // leaf records in schedule order
+    DevBuf<unsigned long long> d_leafcnt{&dev_bytes};   // accepted tasks counted by the emitting kernels (one word)
+    DevBuf<double> d_mkey[2] = {DevBuf<double>{&dev_bytes}, DevBuf<double>{&dev_bytes}};       // sort keys in / out
+    DevBuf<unsigned> d_midx[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}}; // leaf indices in / out
+    DevBuf<unsigned char> d_msort{&dev_bytes};      // the sort's scratch
+    DevBuf<double2> d_mparts{&dev_bytes};           // the scan's block partials
     BatchRings batch{&dev_bytes};      // the batch front end's rings and pinned copies (grown by its calls)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
     // rows on the device beside d_bounds, and their pinned staging ring
@@ -2080,7 +2087,7 @@ static int fold_pending(aq_ctx* ctx) {
 
 static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint32_t n_in, const uint32_t* d_n_in,
                            double* d_out, uint32_t cap_out, double eps, int depth, int max_depth, uint32_t* d_n_out,
-                           double* d_acc) {
+                           double* d_acc, const LeafSink* sink = nullptr) {
     if (!ctx || !d_n_out || !d_acc || (n_in && (!d_in || !d_out))) return AQ_EINVAL;
     if (!integrand_ok(integrand)) return AQ_EINVAL;
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
@@ -2095,8 +2102,14 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
         return rc;
     LevelPart* rows = ctx->d_lparts + ctx->lp_pending;
     with_fid(integrand, [&](auto F) {
-        hipLaunchKernelGGL((k_level_step<decltype(F)::value>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream, (const Rec*)d_in,
-                           n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows, ctx->d_tab, d_n_in);
+        if (sink)   // the leaf-emitting form (aq_integrate_mesh)
+            hipLaunchKernelGGL((k_level_step<decltype(F)::value, LeafSink>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
+                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
+                               ctx->d_tab, d_n_in, *sink);
+        else
+            hipLaunchKernelGGL((k_level_step<decltype(F)::value>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
+                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
+                               ctx->d_tab, d_n_in);
     });
     AQ_HIP(hipGetLastError());
     ctx->lp_pending += grid;
@@ -2124,23 +2137,37 @@ int aq_level_step_chained(aq_ctx* ctx, int integrand, const double* d_in, const 
                            d_acc);
 }
 
-int aq_level_narrow(aq_ctx* ctx, int integrand, double* d_buf0, double* d_buf1, uint32_t cap, uint32_t* d_counts,
-                    int depth, int levels, double eps, int max_depth, double* d_acc) {
+static int level_narrow_impl(aq_ctx* ctx, int integrand, double* d_buf0, double* d_buf1, uint32_t cap,
+                             uint32_t* d_counts, int depth, int levels, double eps, int max_depth, double* d_acc,
+                             const LeafSink* sink) {
     if (!ctx || !d_buf0 || !d_buf1 || !d_counts || !d_acc || levels < 0) return AQ_EINVAL;
     if (!integrand_ok(integrand)) return AQ_EINVAL;
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
     if (levels == 0) return AQ_OK;
     AQ_HIP(hipSetDevice(ctx->device));
     with_fid(integrand, [&](auto F) {
-        hipLaunchKernelGGL((k_level_narrow<decltype(F)::value>), dim3(1), dim3(NARROW_T), 0, ctx->stream, (Rec*)d_buf0,
-                           (Rec*)d_buf1, cap, d_counts, depth, levels, eps, max_depth, d_acc, ctx->d_tab);
+        if (sink)
+            hipLaunchKernelGGL((k_level_narrow<decltype(F)::value, LeafSink>), dim3(1), dim3(NARROW_T), 0, ctx->stream,
+                               (Rec*)d_buf0, (Rec*)d_buf1, cap, d_counts, depth, levels, eps, max_depth, d_acc,
+                               ctx->d_tab, *sink);
+        else
+            hipLaunchKernelGGL((k_level_narrow<decltype(F)::value>), dim3(1), dim3(NARROW_T), 0, ctx->stream,
+                               (Rec*)d_buf0, (Rec*)d_buf1, cap, d_counts, depth, levels, eps, max_depth, d_acc,
+                               ctx->d_tab);
     });
     AQ_HIP(hipGetLastError());
     return AQ_OK;
 }
 
-int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sync_every, aq_result* res,
-                          uint64_t* tpl, uint64_t* lpl, int maxlev) {
+int aq_level_narrow(aq_ctx* ctx, int integrand, double* d_buf0, double* d_buf1, uint32_t cap, uint32_t* d_counts,
+                    int depth, int levels, double eps, int max_depth, double* d_acc) {
+    return level_narrow_impl(ctx, integrand, d_buf0, d_buf1, cap, d_counts, depth, levels, eps, max_depth, d_acc,
+                             nullptr);
+}
+
+// aq_frontier_integrate's run; with `sink`, the same run through the leaf-emitting kernels (aq_integrate_mesh).
+static int frontier_run(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sync_every, aq_result* res,
+                        uint64_t* tpl, uint64_t* lpl, int maxlev, const LeafSink* sink) {
     // The frontier engine of ppls_amd/frontier.py for ONE GPU with its host loop in C: the root, the
     // narrow top in one launch, then chained level steps (device counts, deferred folds) with a host
     // look at the frontier size every sync_every levels -- the Python loop's per-level torch / ctypes
@@ -2164,7 +2191,8 @@ int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sy
     const bool defer0 = ctx->defer_fold;
     ctx->defer_fold = true;
     int depth = std::min(13, max_depth - 1);   // the narrow top (<= 2^12 records a level): one launch
-    if (depth > 0 && (rc = aq_level_narrow(ctx, p->integrand, buf[0], buf[1], cap, cnt, 0, depth, p->eps, max_depth, acc))) {
+    if (depth > 0 &&
+        (rc = level_narrow_impl(ctx, p->integrand, buf[0], buf[1], cap, cnt, 0, depth, p->eps, max_depth, acc, sink))) {
         ctx->defer_fold = defer0;
         return rc;
     }
@@ -2174,7 +2202,7 @@ int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sy
     int since = 0;
     while (depth <= max_depth && depth < AQ_MAX_LEVELS) {
         rc = level_step_impl(ctx, p->integrand, buf[depth & 1], (uint32_t)bound, cnt + depth, buf[(depth + 1) & 1], cap,
-                             p->eps, depth, max_depth, cnt + depth + 1, acc);
+                             p->eps, depth, max_depth, cnt + depth + 1, acc, sink);
         if (rc) break;
         ++depth;
         bound = std::min<unsigned long long>(2 * bound, cap);
@@ -2215,6 +2243,87 @@ int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sy
     if (rc) return rc;
     if (c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
     return aq_level_histogram(ctx, tpl, lpl, maxlev);
+}
+
+int aq_frontier_integrate(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sync_every, aq_result* res,
+                          uint64_t* tpl, uint64_t* lpl, int maxlev) {
+    return frontier_run(ctx, p, cap, sync_every, res, tpl, lpl, maxlev, nullptr);
+}
+
+// The accepted mesh: the frontier run through the leaf-emitting kernels, then leaves -> sorted nodes (aquad.hip
+// k_mesh_*). Everything after the run is enqueued on the context's stream and waited for once.
+int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, int sync_every, uint64_t cap_nodes,
+                      const aq_mesh_io* io, aq_result* res, uint64_t* n_nodes) {
+    if (!ctx || !p || !io || !n_nodes || !io->x || !io->f || !io->cum) return AQ_EINVAL;
+    if (cap_nodes < 3 || cap_nodes > (1ull << 31)) return AQ_EINVAL;
+    if (frontier_cap < 2 || sync_every < 1) return AQ_EINVAL;
+    int rc = validate(p);
+    if (rc) return rc;
+    if (p->integrand == AQ_F_PARAM) return AQ_EINVAL;   // the frontier engine takes no theta
+    *n_nodes = 0;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const size_t cap_leaves = (size_t)((cap_nodes - 1) / 2);
+    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
+    AQ_HIP(ctx->d_leafcnt.grow(1));
+    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    const LeafSink sink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves};
+    aq_result local{};
+    aq_result* r = res ? res : &local;
+    if ((rc = frontier_run(ctx, p, frontier_cap, sync_every, r, nullptr, nullptr, 0, &sink))) return rc;
+    const uint64_t leaves = r->accepted;   // every accepted task emitted (or, past the capacity, counted) one leaf
+    *n_nodes = 2 * leaves + 1;
+    if (*n_nodes > cap_nodes) return AQ_EOVERFLOW;
+    const unsigned n = (unsigned)leaves;
+    const unsigned grid = (n + MESH_T - 1) / MESH_T;
+    hipError_t he = hipSuccess;
+    const size_t sort_bytes = mesh_sort_scratch_bytes(n, &he);
+    AQ_HIP(he);
+    for (int k = 0; k < 2; ++k) {
+        AQ_HIP(ctx->d_mkey[k].grow(n));
+        AQ_HIP(ctx->d_midx[k].grow(n));
+    }
+    AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
+    AQ_HIP(ctx->d_mparts.grow(grid));
+    hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), n,
+                       ctx->d_mkey[0].get(), ctx->d_midx[0].get());
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], n,
+                     ctx->stream));
+    // node pairs go out as one 16-byte store where the caller's arrays allow
+    const bool vec = (((uintptr_t)io->x | (uintptr_t)io->f | (uintptr_t)io->cum) & 15u) == 0;
+    const Leaf* lv = ctx->d_leaf;
+    const unsigned* idx = ctx->d_midx[1];
+    double2* parts = ctx->d_mparts;
+    if (vec)
+        hipLaunchKernelGGL(k_mesh_expand<true>, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, n, io->x, io->f,
+                           io->cum, io->level, parts);
+    else
+        hipLaunchKernelGGL(k_mesh_expand<false>, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, n, io->x, io->f,
+                           io->cum, io->level, parts);
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_scan_parts, dim3(1), dim3(MESH_T), 0, ctx->stream, parts, grid);
+    AQ_HIP(hipGetLastError());
+    if (vec)
+        hipLaunchKernelGGL(k_mesh_cum<true>, dim3(grid), dim3(MESH_T), 0, ctx->stream, n, io->cum, (const double2*)parts);
+    else
+        hipLaunchKernelGGL(k_mesh_cum<false>, dim3(grid), dim3(MESH_T), 0, ctx->stream, n, io->cum, (const double2*)parts);
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
+int aq_mesh_eval(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const double* d_f, const double* d_cum, size_t nq,
+                 const double* d_q, double* d_out) {
+    if (!ctx || n_nodes < 3) return AQ_EINVAL;
+    if (nq > 0 && (!d_x || !d_f || !d_cum || !d_q || !d_out)) return AQ_EINVAL;
+    if (nq == 0) return AQ_OK;
+    const size_t grid = (nq + 255) / 256;
+    if (grid > 0x7fffffffull) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_mesh_eval, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (unsigned long long)n_nodes, d_x,
+                       d_f, d_cum, nq, d_q, d_out);
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
 }
 
 int aq_kernel_timing(aq_ctx* ctx, int enable) {

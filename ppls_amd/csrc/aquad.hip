@@ -2,7 +2,8 @@
 //
 // The design -- sibling pairs, one wavefront per worker with its own LDS ring, cellar / pool / HBM queue,
 // wave-local seeding, exact area accumulators -- is described at the top of aq_stream.h (k_stream). This file
-// holds the other kernels (batch size ordering, level and frontier paths, gather / reset / read-back).
+// holds the other kernels (batch size ordering, level and frontier paths, the accepted mesh, gather / reset /
+// read-back).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (ppls_amd/build.py).
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 #include "aq_stream.h"
 #include "aq_launch_plan.h"
 #include "aq_host_pool.h"
+#include "aq_mesh_sort.h"
 
 #include <rccl/rccl.h>
 
@@ -396,13 +398,36 @@ constexpr int LEVEL_T = AQ_LEVEL_T;
 #endif
 constexpr int LEVEL_NW = LEVEL_T / 64;
 
-template <int FID>
+// The accepted mesh (aq_integrate_mesh): in their leaf-emitting form (MESH) the two level kernels append one
+// record per ACCEPTED task to a leaf buffer -- all that rebuilds its two panels bit for bit, F(mid) included, so
+// nothing is evaluated again -- in schedule order; k_mesh_* below put them in x order. `count` counts every
+// accepted task, `cap` bounds the records stored: past it a lane only counts.
+struct Leaf {
+    double l, r, fl, fmid, fr;
+    unsigned long long depth;
+};
+struct LeafSink {
+    Leaf* buf;
+    unsigned long long* count;
+    unsigned long long cap;
+};
+
+// A level kernel's leaf-emitting form is its instance with ONE trailing LeafSink argument (k_level_step<FID,
+// LeafSink>); k_level_step<FID> has an empty pack: no argument, no leaf word, the kernel as it always was.
+__device__ __forceinline__ const LeafSink& leaf_sink(const LeafSink& s) { return s; }
+
+template <int FID, typename... Sink>
 __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ in, unsigned n_in, Rec* __restrict__ out,
                                                     unsigned* __restrict__ n_out, unsigned cap_out, double eps,
                                                     int depth, int max_depth, LevelPart* __restrict__ parts,
                                                     const ExpPair* __restrict__ gtab,
-                                                    const unsigned* __restrict__ n_in_dev) {
+                                                    const unsigned* __restrict__ n_in_dev, Sink... sink) {
     constexpr int R = LEVEL_R;
+    constexpr bool MESH = sizeof...(Sink) == 1;
+    static_assert(sizeof...(Sink) <= 1, "at most one LeafSink");
+    constexpr int LW = MESH ? LEVEL_NW : 1;
+    __shared__ unsigned s_wl[2][LW];              // MESH: the waves' accepted counts of a chunk, by chunk parity
+    __shared__ unsigned long long s_lbase[2];     // MESH: the chunk's first leaf slot
     // chained levels: the count a previous step appended (read once; uniform), clamped to n_in = the
     // host's bound (<= the input buffer's capacity; a count beyond it was flagged as an overflow)
     if (n_in_dev) n_in = min(*n_in_dev, n_in);
@@ -448,6 +473,10 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
         unsigned long long m[R];
         unsigned c[R + 1];
         c[0] = 0;
+        bool leaf[MESH ? R : 1];
+        unsigned long long ml[MESH ? R : 1];
+        unsigned cl[MESH ? R + 1 : 1];
+        cl[0] = 0;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const double mid = x[k], fmid = f[k];
@@ -469,16 +498,42 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
             }
             m[k] = __ballot(refine[k]);
             c[k + 1] = c[k] + (unsigned)__popcll(m[k]);
+            if constexpr (MESH) {
+                leaf[k] = active[k] && !ref;
+                ml[k] = __ballot(leaf[k]);
+                cl[k + 1] = cl[k] + (unsigned)__popcll(ml[k]);
+            }
         }
         // the chunk's offset: one atomic per block and chunk
         if (lane_id() == 0) s_wc[parity][w] = c[R];
+        if constexpr (MESH) {
+            if (lane_id() == 0) s_wl[parity][w] = cl[R];
+        }
         __syncthreads();
         if (threadIdx.x == 0) {   // one atomic for the block's chunk
             unsigned tot = 0;
             for (int v = 0; v < LEVEL_NW; ++v) tot += s_wc[parity][v];
             s_base[parity] = tot ? atomicAdd(n_out, 2u * tot) : 0u;
+            if constexpr (MESH) {   // ... and one for its leaves (64-bit: the count goes on past the capacity)
+                unsigned totl = 0;
+                for (int v = 0; v < LEVEL_NW; ++v) totl += s_wl[parity][v];
+                s_lbase[parity] = totl ? atomicAdd(leaf_sink(sink...).count, (unsigned long long)totl) : 0ull;
+            }
         }
         __syncthreads();
+        if constexpr (MESH) {
+            const LeafSink& ls = leaf_sink(sink...);
+            unsigned long long loff = s_lbase[parity];
+            for (unsigned v = 0; v < w; ++v) loff += s_wl[parity][v];
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                if (leaf[k]) {
+                    const unsigned long long pos = loff + cl[k] + mbcnt(ml[k]);
+                    if (pos < ls.cap)
+                        ls.buf[pos] = Leaf{rc[k].l, rc[k].r, rc[k].fl, f[k], rc[k].fr, (unsigned long long)depth};
+                }
+            }
+        }
         unsigned off = s_base[parity];
         for (unsigned v = 0; v < w; ++v) off += 2u * s_wc[parity][v];
 #pragma unroll
@@ -560,12 +615,20 @@ __global__ __launch_bounds__(FOLD_T) void k_level_fold(const LevelPart* __restri
 // latency-bound as one launch per level, 2 launches each with the fold). The block's accumulators go
 // into d_acc once at the end, as k_level_fold's would.
 constexpr int NARROW_T = 1024;
-template <int FID>
+// MESH: the accepted records' leaves go to `sink` behind the block-wide prefix the children use -- the launch is
+// one workgroup and runs alone on its stream, so the leaf count is read once, carried block-uniform, and
+// written back at the end: no atomic.
+template <int FID, typename... Sink>
 __global__ __launch_bounds__(NARROW_T) void k_level_narrow(Rec* __restrict__ buf0, Rec* __restrict__ buf1, unsigned cap,
                                                            unsigned* __restrict__ counts, int d0, int levels, double eps,
                                                            int max_depth, double* __restrict__ acc,
-                                                           const ExpPair* __restrict__ gtab) {
+                                                           const ExpPair* __restrict__ gtab, Sink... sink) {
     constexpr int NWV = NARROW_T / 64;
+    constexpr bool MESH = sizeof...(Sink) == 1;
+    static_assert(sizeof...(Sink) <= 1, "at most one LeafSink");
+    __shared__ unsigned s_wl[MESH ? NWV : 1];
+    unsigned long long n_leaf = 0;   // MESH: leaves so far (block-uniform)
+    if constexpr (MESH) n_leaf = *leaf_sink(sink...).count;
     __shared__ ExpEntry tab[ftab_entries<FID>()];
     __shared__ unsigned s_wc[NWV];
     __shared__ unsigned s_n;
@@ -607,12 +670,29 @@ __global__ __launch_bounds__(NARROW_T) void k_level_narrow(Rec* __restrict__ buf
             }
             const unsigned long long m = __ballot(refine);
             if (lane_id() == 0) s_wc[w] = (unsigned)__popcll(m);
+            const bool leaf = MESH && active && !(fabs((larea + rarea) - lrarea) > eps);
+            unsigned long long ml = 0;
+            if constexpr (MESH) {
+                ml = __ballot(leaf);
+                if (lane_id() == 0) s_wl[w] = (unsigned)__popcll(ml);
+            }
             __syncthreads();
             unsigned off = n_ref, tot = 0;
             for (unsigned v = 0; v < (unsigned)NWV; ++v) {
                 const unsigned c = s_wc[v];
                 off += v < w ? c : 0u;
                 tot += c;
+            }
+            if constexpr (MESH) {
+                unsigned long long loff = n_leaf;
+                for (unsigned v = 0; v < (unsigned)NWV; ++v) {
+                    const unsigned c = s_wl[v];
+                    loff += v < w ? c : 0u;
+                    n_leaf += c;
+                }
+                const unsigned long long pos = loff + mbcnt(ml);
+                if (leaf && pos < leaf_sink(sink...).cap)
+                    leaf_sink(sink...).buf[pos] = Leaf{rc.l, rc.r, rc.fl, f[0], rc.fr, (unsigned long long)depth};
             }
             __syncthreads();   // s_wc is rewritten by the next chunk
             if (refine) {
@@ -647,6 +727,7 @@ __global__ __launch_bounds__(NARROW_T) void k_level_narrow(Rec* __restrict__ buf
         acc[0] = H; acc[1] = L; acc[2] += (double)T; acc[3] += (double)A;
         acc[4] = (double)((unsigned)acc[4] | E);
         acc[5] = fmax(acc[5], (double)V);
+        if constexpr (MESH) *leaf_sink(sink...).count = n_leaf;
     }
 }
 
@@ -656,6 +737,174 @@ __global__ __launch_bounds__(64) void k_frontier_root(double a, double b, Rec* o
     stage_f_table<FID>(tab, gtab);
     __syncthreads();
     if (threadIdx.x == 0) out[0] = Rec{a, b, integrand<FID>(a, tab), integrand<FID>(b, tab)};
+}
+
+// ------------------------------------------------------------------------------------------------
+// The accepted mesh: leaves (schedule order) -> nodes in x order with the running integral.
+//   k_mesh_keys      key = the leaf's l, value = its index (sorted by aq_mesh_sort.hip, keys are unique)
+//   k_mesh_expand    one sorted leaf per lane: x, f, level of its two panels; its two terms larea and
+//                    larea + rarea (:189-190, :199, as k_level_step writes them) parked in cum[2j + 1] and
+//                    cum[2j]; the block's double-double sum of larea + rarea
+//   k_mesh_scan_parts  one block: exclusive double-double scan of the block sums, in place
+//   k_mesh_cum       the parked terms back (one 16-byte load per lane), block scan, cum[2j] = P_j and
+//                    cum[2j + 1] = P_j + larea_j rounded once each; the last leaf adds the closing node
+// The scan's tree depends on the leaf count alone (MESH_T leaves per block, lanes in order, a shuffle scan per
+// wave, the waves in order; the partials in fixed contiguous shares), so cum is bit-identical from run to run.
+// ------------------------------------------------------------------------------------------------
+constexpr int MESH_T = 256;
+constexpr int MESH_NW = MESH_T / 64;
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_keys(const Leaf* __restrict__ leaves, unsigned n,
+                                                      double* __restrict__ keys, unsigned* __restrict__ idx) {
+    const unsigned i = blockIdx.x * MESH_T + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = leaves[i].l;
+    idx[i] = i;
+}
+
+// Inclusive double-double scan over the block's lanes in thread order; `tot` receives the block's sum.
+__device__ __forceinline__ void mesh_block_scan(double& hi, double& lo, double& tot_hi, double& tot_lo) {
+    __shared__ double s_h[MESH_NW], s_l[MESH_NW];
+    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double h2 = __shfl_up(hi, o, 64), l2 = __shfl_up(lo, o, 64);
+        if (lane >= (unsigned)o) dd_add_dd(hi, lo, h2, l2);
+    }
+    if (lane == 63) { s_h[w] = hi; s_l[w] = lo; }
+    __syncthreads();
+    double ph = 0.0, pl = 0.0;   // the waves before this one, in order
+    tot_hi = 0.0; tot_lo = 0.0;
+    for (unsigned v = 0; v < (unsigned)MESH_NW; ++v) {
+        if (v == w) { ph = tot_hi; pl = tot_lo; }
+        dd_add_dd(tot_hi, tot_lo, s_h[v], s_l[v]);
+    }
+    dd_add_dd(ph, pl, hi, lo);
+    hi = ph; lo = pl;
+    __syncthreads();   // s_h / s_l may be written again
+}
+
+// VEC: x, f and cum are 16-byte aligned (node pairs 2j, 2j + 1 go out as one double2).
+template <bool VEC>
+__device__ __forceinline__ void mesh_store2(double* __restrict__ p, size_t j, double v0, double v1) {
+    if constexpr (VEC) {
+        reinterpret_cast<double2*>(p)[j] = make_double2(v0, v1);
+    } else {
+        p[2 * j] = v0;
+        p[2 * j + 1] = v1;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MESH_T) void k_mesh_expand(const Leaf* __restrict__ leaves, const unsigned* __restrict__ idx,
+                                                        unsigned n, double* __restrict__ x, double* __restrict__ f,
+                                                        double* __restrict__ cum, unsigned char* __restrict__ level,
+                                                        double2* __restrict__ parts) {
+    const unsigned j = blockIdx.x * MESH_T + threadIdx.x;
+    double hi = 0.0, lo = 0.0;
+    if (j < n) {
+        const Leaf lf = leaves[idx[j]];
+        const double mid = (lf.l + lf.r) / 2;                          // :187
+        const double larea = (lf.fl + lf.fmid) * (mid - lf.l) / 2;     // :189
+        const double rarea = (lf.fmid + lf.fr) * (lf.r - mid) / 2;     // :190
+        hi = larea + rarea;                                            // :199
+        mesh_store2<VEC>(x, j, lf.l, mid);
+        mesh_store2<VEC>(f, j, lf.fl, lf.fmid);
+        mesh_store2<VEC>(cum, j, hi, larea);
+        if (level) {
+            level[2 * (size_t)j] = (unsigned char)lf.depth;
+            level[2 * (size_t)j + 1] = (unsigned char)lf.depth;
+        }
+        if (j == n - 1) {   // the closing node (its cum: k_mesh_cum)
+            x[2 * (size_t)n] = lf.r;
+            f[2 * (size_t)n] = lf.fr;
+        }
+    }
+    double th, tl;
+    mesh_block_scan(hi, lo, th, tl);
+    if (threadIdx.x == 0) parts[blockIdx.x] = make_double2(th, tl);
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_scan_parts(double2* __restrict__ parts, unsigned nparts) {
+    // thread t owns the contiguous share [t * per, (t + 1) * per)
+    const unsigned per = (nparts + MESH_T - 1) / MESH_T;
+    const unsigned b0 = min(threadIdx.x * per, nparts), b1 = min(b0 + per, nparts);
+    double hi = 0.0, lo = 0.0;
+    for (unsigned i = b0; i < b1; ++i) {
+        const double2 p = parts[i];
+        dd_add_dd(hi, lo, p.x, p.y);
+    }
+    double th, tl;
+    mesh_block_scan(hi, lo, th, tl);
+    // the share's exclusive prefix is the inclusive one of the thread before (nothing is subtracted)
+    __shared__ double s_eh[MESH_T], s_el[MESH_T];
+    s_eh[threadIdx.x] = hi; s_el[threadIdx.x] = lo;
+    __syncthreads();
+    double eh = 0.0, el = 0.0;
+    if (threadIdx.x > 0) { eh = s_eh[threadIdx.x - 1]; el = s_el[threadIdx.x - 1]; }
+    for (unsigned i = b0; i < b1; ++i) {
+        const double2 p = parts[i];
+        parts[i] = make_double2(eh, el);
+        dd_add_dd(eh, el, p.x, p.y);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MESH_T) void k_mesh_cum(unsigned n, double* __restrict__ cum,
+                                                     const double2* __restrict__ parts) {
+    const unsigned j = blockIdx.x * MESH_T + threadIdx.x;
+    double area = 0.0, larea = 0.0;
+    if (j < n) {
+        if constexpr (VEC) {
+            const double2 t = reinterpret_cast<const double2*>(cum)[j];
+            area = t.x; larea = t.y;
+        } else {
+            area = cum[2 * (size_t)j]; larea = cum[2 * (size_t)j + 1];
+        }
+    }
+    double hi = area, lo = 0.0, th, tl;
+    mesh_block_scan(hi, lo, th, tl);
+    __shared__ double s_ih[MESH_T], s_il[MESH_T];   // every lane's inclusive prefix, for the lane after it
+    s_ih[threadIdx.x] = hi; s_il[threadIdx.x] = lo;
+    __syncthreads();
+    if (j >= n) return;
+    const double2 base = parts[blockIdx.x];
+    double ih = base.x, il = base.y;          // P_{j+1}: the blocks before, then this block's inclusive prefix
+    dd_add_dd(ih, il, hi, lo);
+    // P_j: the blocks before and the inclusive prefix of the lane before (the block's first lane: the base alone)
+    double ph = base.x, pl = base.y;
+    if (threadIdx.x > 0) dd_add_dd(ph, pl, s_ih[threadIdx.x - 1], s_il[threadIdx.x - 1]);
+    double mh = ph, ml = pl;
+    dd_add_dd(mh, ml, larea, 0.0);
+    mesh_store2<VEC>(cum, j, ph + pl, mh + ml);
+    if (j == n - 1) cum[2 * (size_t)n] = ih + il;
+}
+
+// Integral from x_0 to q on a mesh (aq_mesh_eval): the trapezoid rule on the partial panel, one IEEE operation
+// per step (the file is built with -ffp-contract=off). One query per lane, a binary search over x for the last
+// node <= q among 0 .. m - 1.
+__global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, const double* __restrict__ x,
+                                                   const double* __restrict__ f, const double* __restrict__ cum,
+                                                   size_t nq, const double* __restrict__ q, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const double qq = q[i];
+    const unsigned long long m = n_nodes - 1;
+    if (!(qq >= x[0] && qq <= x[m])) {   // outside, or NaN
+        out[i] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    unsigned long long lo = 0, hi = m - 1;   // x[lo] <= q; the answer is in [lo, hi]
+    while (lo < hi) {
+        const unsigned long long mid = lo + (hi - lo + 1) / 2;
+        if (x[mid] <= qq) lo = mid;
+        else hi = mid - 1;
+    }
+    const double xk = x[lo], fk = f[lo];
+    const double h = qq - xk;
+    const double w = x[lo + 1] - xk;
+    const double fq = fk + (f[lo + 1] - fk) * (h / w);
+    out[i] = cum[lo] + (fk + fq) * h / 2;
 }
 
 // Gather n slots' totals into a caller device buffer as f64 [area, tasks, accepted, error] rows,
