@@ -2,8 +2,8 @@
 // Host side: the C ABI of include/aquad.h (included by aquad.hip after the kernels).
 // ================================================================================================
 #include "aq_host_args.h"   // the argument rules and the chunk schedule (no HIP: tests/test_host_args.py)
-#include "aq_batch_plan.h"  // the batch front end's pipeline: steps, streams, events (no HIP: tests/test_batch_plan.py)
-#include "aq_device_batch_plan.h"   // ... and the device-resident batch's (no HIP: tests/test_device_batch_plan.py)
+#include "aq_batch_plan.h"  // the batch pipelines, host and device-resident: steps, streams, events (no HIP:
+                            // tests/test_batch_plan.py, tests/test_device_batch_plan.py)
 #include "aq_host_mem.h"    // owning device / pinned buffers, events, streams
 
 using namespace aq;
@@ -68,124 +68,112 @@ struct HostOut {
     unsigned long long cu[AQ_CU_SLOTS] = {};
 };
 
-// The batch front end's buffers (aq_integrate_batch, _params, _err). The device keeps rings of two chunks,
-// indexed by chunk parity and `R` rows apart -- bounds, rows {area, tasks, accepted, error}, theta, error sums,
-// size order and its permutation -- and one chunk's size keys, for the largest chunk so far (grow-only up to
-// MAXK rows, whatever n: ADVICE r5 -- they had been sized to the whole batch, 72 B per integral); the pinned
-// host copies cover the whole call (grow-only). Who may touch which parity when: aq_batch_plan.h.
+// The device rings both batch pipelines keep, each its own set (a call of the host batch may follow a
+// device-resident one still in flight without waiting): two chunks, indexed by chunk parity and `R` rows apart
+// -- bounds, theta, size order and its permutation -- and one chunk's size keys. Who may touch which parity
+// when: aq_batch_plan.h.
 struct BatchRings {
-    DevBuf<double> rows;        // [2][R][4]
     DevBuf<double2> bounds;     // [2][R]
     DevBuf<double2> sorted;     // [2][R] the chunk's bounds in size order (k_batch_scatter)
     DevBuf<unsigned> key;       // [R] size class per integral (k_batch_estimate)
     DevBuf<unsigned> perm;      // [2][R] sorted position -> integral
     DevBuf<unsigned> cnt;       // [2] x (EST_KEYS counts + EST_KEYS cursors)
     DevBuf<double> est;         // [2] the chunk's sum of size estimates
-    DevBuf<double> theta;       // [2][R][nparams] (the first aq_integrate_batch_params)
+    DevBuf<double> theta;       // [2][R][nparams] (the first AQ_F_PARAM call)
     DevBuf<double> thsorted;    // [2][R][nparams] (k_batch_scatter_theta)
-    DevBuf<double> errrows;     // [2][R][2] {err_abs, err_signed} (the first aq_integrate_batch_err)
-    PinBuf<double> h_rows;      // [n][4]
-    PinBuf<double2> h_bounds;   // [n]
-    PinBuf<double> h_theta;     // [n][nparams]
-    PinBuf<double> h_errrows;   // [n][2]
-    size_t R = 0;               // the current call's largest chunk (every ring holds at least two of it)
-    bool par = false, err = false;   // ... and whether theta rows / error rows travel in it
+    size_t R = 0;               // the current call's rows per parity
+    bool par = false;           // ... and whether theta rows travel in it
     explicit BatchRings(unsigned long long* bytes)
-        : rows{bytes}, bounds{bytes}, sorted{bytes}, key{bytes}, perm{bytes}, cnt{bytes}, est{bytes}, theta{bytes},
-          thsorted{bytes}, errrows{bytes} {}
+        : bounds{bytes}, sorted{bytes}, key{bytes}, perm{bytes}, cnt{bytes}, est{bytes}, theta{bytes}, thsorted{bytes} {}
 
-    // for a call of n integrals in chunks of at most `chunk_rows`, with theta rows (par_) and error rows (err_)
-    int grow(size_t chunk_rows, size_t n, bool par_, bool err_) {
+    // for a call with chunks of at most `rows` (grow-only: nothing happens once they hold as much)
+    int grow(size_t rows, bool par_) {
         constexpr size_t NP = (size_t)param::nparams;
-        R = chunk_rows, par = par_, err = err_;
-        AQ_HIP(rows.grow(8 * R));
+        R = rows, par = par_;
         AQ_HIP(bounds.grow(2 * R));
         AQ_HIP(sorted.grow(2 * R));
         AQ_HIP(key.grow(R));
         AQ_HIP(perm.grow(2 * R));
         AQ_HIP(cnt.grow(4 * EST_KEYS));
         AQ_HIP(est.grow(2));
-        AQ_HIP(h_rows.grow(4 * n));
-        AQ_HIP(h_bounds.grow(n));
         if (par) {
             AQ_HIP(theta.grow(NP * 2 * R));
             AQ_HIP(thsorted.grow(NP * 2 * R));
-            AQ_HIP(h_theta.grow(NP * n));
         }
+        return AQ_OK;
+    }
+
+    // chunk c's places in the rings (null where the call has none: theta)
+    struct View {
+        double2 *bounds, *sorted;
+        unsigned *perm, *cnt, *cnt_next;   // (cnt_next, est_next: the other parity's, which the scatter zeroes)
+        double *est, *est_next, *theta, *thsorted;
+    };
+    View at(size_t c) const {
+        constexpr size_t NP = (size_t)param::nparams;
+        const size_t p = c & 1u;
+        return View{bounds + p * R, sorted + p * R, perm + p * R, cnt + 2 * EST_KEYS * p, cnt + 2 * EST_KEYS * (p ^ 1u),
+                    est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr, par ? thsorted + p * R * NP : nullptr};
+    }
+};
+
+// The host batch's buffers (aq_integrate_batch, _params, _err): the rings for the largest chunk so far (grow-only
+// up to MAXK rows, whatever n: ADVICE r5 -- they had been sized to the whole batch, 72 B per integral), with rings
+// of rows {area, tasks, accepted, error} and error sums beside them; the pinned host copies cover the whole call
+// (grow-only).
+struct HostBatch : BatchRings {
+    DevBuf<double> rows;        // [2][R][4]
+    DevBuf<double> errrows;     // [2][R][2] {err_abs, err_signed} (the first aq_integrate_batch_err)
+    PinBuf<double> h_rows;      // [n][4]
+    PinBuf<double2> h_bounds;   // [n]
+    PinBuf<double> h_theta;     // [n][nparams]
+    PinBuf<double> h_errrows;   // [n][2]
+    bool err = false;           // error rows travel in the current call
+    explicit HostBatch(unsigned long long* bytes) : BatchRings{bytes}, rows{bytes}, errrows{bytes} {}
+
+    // for a call of n integrals in chunks of at most `chunk_rows`, with theta rows (par_) and error rows (err_)
+    int grow(size_t chunk_rows, size_t n, bool par_, bool err_) {
+        constexpr size_t NP = (size_t)param::nparams;
+        if (int rc = BatchRings::grow(chunk_rows, par_)) return rc;
+        err = err_;
+        AQ_HIP(rows.grow(8 * R));
+        AQ_HIP(h_rows.grow(4 * n));
+        AQ_HIP(h_bounds.grow(n));
+        if (par) AQ_HIP(h_theta.grow(NP * n));
         if (err) {
             AQ_HIP(errrows.grow(4 * R));
             AQ_HIP(h_errrows.grow(2 * n));
         }
         return AQ_OK;
     }
-
-    // chunk c's places in the rings (null where the call has none: theta, error rows)
-    struct View {
-        double* rows;
-        double2 *bounds, *sorted;
-        unsigned *perm, *cnt, *cnt_next;   // (cnt_next, est_next: the other parity's, which the scatter zeroes)
-        double *est, *est_next, *theta, *thsorted, *errrows;
-    };
-    View at(size_t c) const {
-        constexpr size_t NP = (size_t)param::nparams;
-        const size_t p = c & 1u;
-        return View{rows + 4 * p * R, bounds + p * R, sorted + p * R, perm + p * R, cnt + 2 * EST_KEYS * p,
-                    cnt + 2 * EST_KEYS * (p ^ 1u), est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr,
-                    par ? thsorted + p * R * NP : nullptr, err ? errrows + 2 * p * R : nullptr};
-    }
+    double* rows_at(size_t c) const { return rows + 4 * (c & 1u) * R; }
+    double* errrows_at(size_t c) const { return err ? errrows + 2 * (c & 1u) * R : nullptr; }
 };
 
-// The device-resident batch's buffers (aq_integrate_batch_device): rings of its own, so that a call of the
-// host batch may follow one still in flight without waiting, and the events its plan names -- the context's,
-// reused from call to call, because the call returns while they are pending. The rings hold two chunks of
-// MAXK rows whatever the call's size: they are allocated once, by the context's first such call (theta and
-// its size-ordered copy by the first AQ_F_PARAM one), and no later call allocates, frees or waits. The layout
-// is BatchRings' (View), plus the check kernel's flag ring and what aq_device_batch_check reads.
-struct DevBatchRings {
-    static constexpr size_t R = (size_t)MAXK;
-    DevBuf<double2> bounds, sorted;   // [2][R]
-    DevBuf<unsigned> key;             // [R]
-    DevBuf<unsigned> perm, flag;      // [2][R]
-    DevBuf<unsigned> cnt;             // [2] x (EST_KEYS counts + EST_KEYS cursors)
-    DevBuf<double> est;               // [2]
-    DevBuf<double> theta, thsorted;   // [2][R][nparams]
+// The device-resident batch's buffers (aq_integrate_batch_device): the rings, the check kernel's flag ring, what
+// aq_device_batch_check reads, and the events its plan names -- the context's, reused from call to call, because
+// the call returns while they are pending. The rings hold two chunks of MAXK rows whatever the call's size: they
+// are allocated once, by the context's first such call (theta and its size-ordered copy by the first AQ_F_PARAM
+// one), and no later call allocates, frees or waits.
+struct DevBatch : BatchRings {
+    DevBuf<unsigned> flag;            // [2][R]
     DevBuf<DevBatchStat> stat;        // one: invalid rows and error bits since the last aq_device_batch_check
     PinBuf<DevBatchStat> h_stat;      // its pinned copy
     std::vector<Event> ev;            // by the plan's event numbers (grow-only)
-    explicit DevBatchRings(unsigned long long* bytes)
-        : bounds{bytes}, sorted{bytes}, key{bytes}, perm{bytes}, flag{bytes}, cnt{bytes}, est{bytes}, theta{bytes},
-          thsorted{bytes}, stat{bytes} {}
+    explicit DevBatch(unsigned long long* bytes) : BatchRings{bytes}, flag{bytes}, stat{bytes} {}
 
-    int ensure(bool par, size_t n_events) {
-        constexpr size_t NP = (size_t)param::nparams;
+    int ensure(bool par_, size_t n_events) {
+        if (int rc = BatchRings::grow((size_t)MAXK, par_)) return rc;
+        AQ_HIP(flag.grow(2 * R));
         if (!stat) {
-            AQ_HIP(bounds.alloc(2 * R, false));
-            AQ_HIP(sorted.alloc(2 * R, false));
-            AQ_HIP(key.alloc(R, false));
-            AQ_HIP(perm.alloc(2 * R, false));
-            AQ_HIP(flag.alloc(2 * R, false));
-            AQ_HIP(cnt.alloc(4 * EST_KEYS, false));
-            AQ_HIP(est.alloc(2, false));
             AQ_HIP(h_stat.alloc(1, true));
             AQ_HIP(stat.alloc(1, true));
-        }
-        if (par && !theta) {
-            AQ_HIP(theta.alloc(NP * 2 * R, false));
-            AQ_HIP(thsorted.alloc(NP * 2 * R, false));
         }
         while (ev.size() < n_events) {
             ev.emplace_back();
             AQ_HIP(ev.back().create(hipEventDisableTiming));
         }
         return AQ_OK;
-    }
-    // chunk c's places in the rings, as BatchRings::at (no row rings: the gather writes the caller's arrays)
-    BatchRings::View at(size_t c, bool par) const {
-        constexpr size_t NP = (size_t)param::nparams;
-        const size_t p = c & 1u;
-        return BatchRings::View{nullptr, bounds + p * R, sorted + p * R, perm + p * R, cnt + 2 * EST_KEYS * p,
-                                cnt + 2 * EST_KEYS * (p ^ 1u), est + p, est + (p ^ 1u), par ? theta + p * R * NP : nullptr,
-                                par ? thsorted + p * R * NP : nullptr, nullptr};
     }
     unsigned* flags(size_t c) const { return flag + (c & 1u) * R; }
 };
@@ -298,7 +286,7 @@ struct aq_ctx {
     DevBuf<unsigned> d_midx[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}}; // leaf indices in / out
     DevBuf<unsigned char> d_msort{&dev_bytes};      // the sort's scratch
     DevBuf<double2> d_mparts{&dev_bytes};           // the scan's block partials
-    BatchRings batch{&dev_bytes};      // the batch front end's rings and pinned copies (grown by its calls)
+    HostBatch batch{&dev_bytes};       // the batch front end's rings and pinned copies (grown by its calls)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
     // rows on the device beside d_bounds, and their pinned staging ring
     DevBuf<double> d_theta{&dev_bytes};      // [NSLOTS_ALL][nparams]
@@ -310,7 +298,7 @@ struct aq_ctx {
     bool slot_err[NSLOTS_ALL] = {};    // slot's last launch was an ERR launch (beside slot_hist)
     int occ_err[4][6] = {};            // the ERR instances' resident workgroups per CU, by Variant (as occ)
     TolBufs tol{&dev_bytes};           // aq_integrate_batch_tol's buffers (allocated by its first call)
-    DevBatchRings devbatch{&dev_bytes};   // aq_integrate_batch_device's rings and events (allocated by its first call)
+    DevBatch devbatch{&dev_bytes};     // aq_integrate_batch_device's rings and events (allocated by its first call)
     // eval buffers (not counted)
     DevBuf<double> d_x, d_y;
     // host staging
@@ -1543,15 +1531,20 @@ static int check_and_stage(aq_ctx* ctx, int integrand, size_t m, const double* a
 // rows[perm ? perm[s] : s] (k_gather_reset) and, behind an ERR launch, its error sums to errrows likewise
 // (k_gather_err; null: not an ERR launch). The kernels return the slots to zero: no k_reset before the next
 // launch, and the slots count as clean.
+// (slots [first, first + k) were returned to zero by a gather kernel -- their error sums too, if err)
+static void mark_clean(aq_ctx* ctx, int first, int k, bool err) {
+    if (err) memset(ctx->err_dirty + first, 0, (size_t)k);
+    memset(ctx->dirty + first, 0, (size_t)k);
+    memset(ctx->parts_dirty + first, 0, (size_t)k);
+}
+
 static int gather_clean(aq_ctx* ctx, int k, double* rows, double* errrows, const unsigned* perm) {
     hipLaunchKernelGGL(k_gather_reset, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_ctl, ctx->d_parts, ctx->grid, 0,
                        k, rows, perm);
     if (errrows)
         hipLaunchKernelGGL(k_gather_err, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, 0, k, errrows, perm);
     AQ_HIP(hipGetLastError());
-    if (errrows) memset(ctx->err_dirty, 0, (size_t)k);
-    memset(ctx->dirty, 0, (size_t)k);
-    memset(ctx->parts_dirty, 0, (size_t)k);
+    mark_clean(ctx, 0, k, errrows != nullptr);
     return AQ_OK;
 }
 
@@ -1625,28 +1618,95 @@ static unsigned unpack_rows(aq_ctx* ctx, size_t m, const double* rows, size_t st
 // while chunk c runs, s_h2d copies it into its own device rows, s_pre puts it into size order (largest trees
 // first: the launch's tail is its smallest jobs; AQ_BATCH_SORT=0: off) as chunk c's launch frees the CUs, the
 // context's stream runs the launches and gathers, s_d2h copies chunk c's rows back while chunk c + 1 runs and
-// the host unpacks chunk c - 1. Which step runs where, behind what: batch_plan (aq_batch_plan.h). BatchCall
-// is one call's state and one function per step kind -- it orders nothing.
+// the host unpacks chunk c - 1. Which step runs where, behind what: batch_plan (aq_batch_plan.h); run_plan
+// walks it. BatchCall is one call's state and one function per step kind -- it orders nothing.
 //
 // theta: the parametrised family's rows [n][nparams] (integrand AQ_F_PARAM), else null; they travel with the
 // bounds. The ERR form's (plan.err) slots' error sums travel with the rows.
-struct BatchCall {
+
+// the workload is fresh: the context holds no measured job-size hint for this integrand and tolerance (the
+// sorted chunks' pre-passes preset the job size until a launch has measured one: aq_batch_plan.h)
+static bool hint_is_fresh(const aq_ctx* ctx, int integrand, double eps) {
+    return ctx->gsplit_env <= 0 &&
+           !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps && ctx->hint.nshards == 1);
+}
+
+// One call of either batch pipeline, and the steps the two run alike.
+struct BatchSteps {
     aq_ctx* ctx;
-    const BatchRings& B;       // ctx->batch
+    const BatchRings& R;       // the pipeline's rings
     const BatchPlan& plan;
-    std::vector<size_t> off;   // chunk c: integrals [off[c], off[c + 1])
-    const double *a, *b, *theta;
     double eps;
     int integrand;
-    RowsOut out;
-    unsigned errbits = 0;
+    const double *a = nullptr, *b = nullptr;   // the bounds on the host (device-resident batch: none)
+    int max_depth = 0;
+    std::vector<size_t> off;   // chunk c: integrals [off[c], off[c + 1])
     static constexpr size_t NP = (size_t)param::nparams;
 
+    BatchSteps(aq_ctx* ctx_, const BatchRings& R_, const BatchPlan& plan_, double eps_, int integrand_)
+        : ctx(ctx_), R(R_), plan(plan_), eps(eps_), integrand(integrand_), off(plan_.chunks.size() + 1, 0) {
+        for (size_t c = 0; c < plan.chunks.size(); ++c) off[c + 1] = off[c] + (size_t)plan.chunks[c];
+    }
     int zero(hipStream_t s) {
-        AQ_HIP(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4 * EST_KEYS, s));
-        AQ_HIP(hipMemsetAsync(B.est, 0, sizeof(double) * 2, s));
+        AQ_HIP(hipMemsetAsync(R.cnt, 0, sizeof(unsigned) * 4 * EST_KEYS, s));
+        AQ_HIP(hipMemsetAsync(R.est, 0, sizeof(double) * 2, s));
         return AQ_OK;
     }
+    int pre(int c, hipStream_t s) {
+        return size_prepass(ctx, integrand, plan.chunks[c], eps, R.at(c), R.key, plan.preset[c], s);
+    }
+    // (without bounds on the host, plan.first_slot keeps every chunk off the per-CU instance, which takes them
+    // as kernel arguments)
+    int launch_chunk(int c) {
+        const BatchRings::View v = R.at(c);
+        LaunchArgs g;   // (no histograms: hist stays false)
+        g.integrand = integrand;
+        g.k = plan.chunks[c];
+        g.a = a ? a + off[c] : nullptr;
+        g.b = b ? b + off[c] : nullptr;
+        g.eps = eps;
+        g.max_depth = max_depth;
+        g.first_slot = plan.first_slot[c];
+        g.dev_bounds = plan.sorted[c] ? v.sorted : v.bounds;
+        g.dev_theta = plan.sorted[c] ? v.thsorted : v.theta;
+        g.err = plan.err;
+        g.heap = true;
+        ctx->hint.preset = plan.preset[c];
+        const int rc = launch(ctx, g);
+        ctx->hint.preset = false;
+        return rc;
+    }
+};
+
+// Walks a plan: for each step that BatchWalk lets run, the waits on the step's stream (on the host for a host
+// step), `step(s, stream)` for what the step does, and its event. streams: by BStream, the host apart; ev: by
+// the plan's event numbers. Returns the call's code.
+extern "C++" template <typename Step>
+static int run_plan(const BatchPlan& plan, const hipStream_t* streams, const Event* ev, Step&& step) {
+    static_assert(AQ_OK == 0, "BatchWalk's success code");
+    BatchWalk walk;   // which steps a failure leaves out
+    for (const BatchStep& s : plan.steps) {
+        if (!walk.runs(s)) continue;
+        const bool host = s.stream == BStream::HOST;
+        const hipStream_t st = host ? nullptr : streams[(int)s.stream];
+        auto issue = [&]() -> int {
+            for (int w : s.wait)
+                if (w >= 0) AQ_HIP(host ? hipEventSynchronize(ev[w]) : hipStreamWaitEvent(st, ev[w], 0));
+            if (int rc = step(s, st)) return rc;
+            if (s.record >= 0) AQ_HIP(hipEventRecord(ev[s.record], st));
+            return AQ_OK;
+        };
+        walk.done(s, issue());
+    }
+    return walk.rc;
+}
+
+struct BatchCall : BatchSteps {
+    const HostBatch& B;        // ctx->batch
+    const double* theta;
+    RowsOut out;
+    unsigned errbits = 0;
+
     // (on several host threads: the first chunk's is the only host work before the device starts, the next
     // ones' must stay shorter than a launch)
     int stage(int c) {
@@ -1662,37 +1722,15 @@ struct BatchCall {
         AQ_HIP(hipMemcpyAsync(v.bounds, B.h_bounds + off[c], sizeof(double2) * m, hipMemcpyHostToDevice, s));
         return AQ_OK;
     }
-    int pre(int c, hipStream_t s) {
-        return size_prepass(ctx, integrand, plan.chunks[c], eps, B.at(c), B.key, plan.preset[c], s);
-    }
-    int launch_chunk(int c) {
-        const BatchRings::View v = B.at(c);
-        LaunchArgs g;   // (no histograms: hist stays false)
-        g.integrand = integrand;
-        g.k = plan.chunks[c];
-        g.a = a + off[c];
-        g.b = b + off[c];
-        g.eps = eps;
-        g.dev_bounds = plan.sorted[c] ? v.sorted : v.bounds;
-        g.dev_theta = plan.sorted[c] ? v.thsorted : v.theta;
-        g.err = plan.err;
-        g.heap = true;
-        ctx->hint.preset = plan.preset[c];
-        const int rc = launch(ctx, g);
-        ctx->hint.preset = false;
-        return rc;
-    }
     // (k_gather_reset writes size-ordered slots back in input order)
     int gather(int c) {
-        const BatchRings::View v = B.at(c);
-        return gather_clean(ctx, plan.chunks[c], v.rows, v.errrows, plan.sorted[c] ? v.perm : nullptr);
+        return gather_clean(ctx, plan.chunks[c], B.rows_at(c), B.errrows_at(c), plan.sorted[c] ? B.at(c).perm : nullptr);
     }
     int d2h(int c, hipStream_t s) {
-        const BatchRings::View v = B.at(c);
         const size_t m = (size_t)plan.chunks[c];
-        AQ_HIP(hipMemcpyAsync(B.h_rows + 4 * off[c], v.rows, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, s));
+        AQ_HIP(hipMemcpyAsync(B.h_rows + 4 * off[c], B.rows_at(c), sizeof(double) * 4 * m, hipMemcpyDeviceToHost, s));
         if (plan.err)
-            AQ_HIP(hipMemcpyAsync(B.h_errrows + 2 * off[c], v.errrows, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, s));
+            AQ_HIP(hipMemcpyAsync(B.h_errrows + 2 * off[c], B.errrows_at(c), sizeof(double) * 2 * m, hipMemcpyDeviceToHost, s));
         return AQ_OK;
     }
     void unpack(int c) {
@@ -1724,54 +1762,44 @@ static int batch_run(aq_ctx* ctx, size_t n, const double* a, const double* b, co
     const std::vector<int> chunks = batch_chunks(n, (size_t)std::max(0, env_int("AQ_BATCH_FIRST", AQ_BATCH_FIRST)),
                                                  (size_t)std::max(0, env_int("AQ_BATCH_LAST", AQ_BATCH_LAST)));
     const bool sort = env_int("AQ_BATCH_SORT", 1) != 0;
-    // (preset while the workload is fresh: no measured hint for this integrand and tolerance)
-    const bool fresh = ctx->gsplit_env <= 0 && !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps &&
-                                                 ctx->hint.nshards == 1);
-    const BatchPlan plan = batch_plan(chunks, sort, par, err, fresh);
+    const BatchPlan plan = batch_plan(chunks, sort, par, err, hint_is_fresh(ctx, integrand, eps));
     int rc = ctx->batch.grow((size_t)*std::max_element(chunks.begin(), chunks.end()), n, par, err);
     if (rc) return rc;
     for (Stream* s : {&ctx->s_h2d, &ctx->s_d2h, &ctx->s_pre})
         if (!*s) AQ_HIP(s->create());
-    const hipStream_t streams[] = {ctx->stream, ctx->s_h2d, ctx->s_d2h, ctx->s_pre};   // by BStream
+    const hipStream_t streams[] = {ctx->stream, ctx->s_h2d, ctx->s_d2h, ctx->s_pre, nullptr};   // by BStream (no caller's)
     // (destroyed on return, after every stream was synchronised: the plan's DRAIN)
     std::vector<Event> ev((size_t)plan.n_events());
     for (Event& e : ev) AQ_HIP(e.create(hipEventDisableTiming));
-    BatchCall call{ctx, ctx->batch, plan, std::vector<size_t>(chunks.size() + 1, 0), a, b, theta, eps, integrand,
+    BatchCall call{BatchSteps(ctx, ctx->batch, plan, eps, integrand), ctx->batch, theta,
                    RowsOut{area, accepted, tasks, err_abs, err_signed}};
-    for (size_t c = 0; c < chunks.size(); ++c) call.off[c + 1] = call.off[c] + (size_t)chunks[c];
-    static_assert(AQ_OK == 0, "BatchWalk's success code");
-    BatchWalk walk;   // which steps a failure leaves out
-    for (const BatchStep& s : plan.steps) {
-        if (!walk.runs(s)) continue;
+    call.a = a, call.b = b;
+    rc = run_plan(plan, streams, ev.data(), [&](const BatchStep& s, hipStream_t st) {
         const int c = s.chunk;
-        const hipStream_t st = s.stream == BStream::HOST ? nullptr : streams[(int)s.stream];
         int r = AQ_OK;
-        for (int w : s.wait)
-            if (w >= 0 && (st ? hipStreamWaitEvent(st, ev[w], 0) : hipEventSynchronize(ev[w])) != hipSuccess) r = AQ_EHIP;
-        if (r == AQ_OK) switch (s.kind) {
+        switch (s.kind) {
             case BKind::START: case BKind::FENCE: break;   // their event is all they do
-            case BKind::ZERO: r = call.zero(st); break;
+            case BKind::ZERO: return call.zero(st);
             case BKind::STAGE:
                 if (c == 0) mark("setup", -1);
-                r = call.stage(c);
-                break;
+                return call.stage(c);
             case BKind::H2D: r = call.h2d(c, st), mark("staged", c); break;
-            case BKind::PRE: r = call.pre(c, st); break;
+            case BKind::PRE: return call.pre(c, st);
             case BKind::LAUNCH: r = call.launch_chunk(c), mark("launched", c); break;
-            case BKind::GATHER: r = call.gather(c); break;
-            case BKind::D2H: r = call.d2h(c, st); break;
+            case BKind::GATHER: return call.gather(c);
+            case BKind::D2H: return call.d2h(c, st);
             case BKind::WAIT: mark("rows on host", c); break;
             case BKind::UNPACK: call.unpack(c), mark("unpacked", c); break;
             case BKind::DRAIN:   // every enqueued chunk finishes before the buffers can be reused or the events destroyed
-                for (hipStream_t x : streams)
-                    if (hipStreamSynchronize(x) != hipSuccess) r = AQ_EHIP;
+                for (int x = 0; x <= (int)BStream::PRE; ++x)
+                    if (hipStreamSynchronize(streams[x]) != hipSuccess) r = AQ_EHIP;
                 mark("device done", -1);
                 break;
+            default: return AQ_EINVAL;   // (no such step in a host plan)
         }
-        if (r == AQ_OK && s.record >= 0 && hipEventRecord(ev[s.record], st) != hipSuccess) r = AQ_EHIP;
-        walk.done(s, r);
-    }
-    if (walk.rc) return walk.rc;
+        return r;
+    });
+    if (rc) return rc;
     if (trace) {
         fprintf(stderr, "aq_integrate_batch n=%zu:", n);
         for (auto& m : tr) fprintf(stderr, " [%s %.1f us]", m.first.c_str(), m.second);
@@ -1802,26 +1830,14 @@ int aq_integrate_batch_err(aq_ctx* ctx, size_t n, const double* a, const double*
 // ---- device-resident batch (aq_integrate_batch_device) ---------------------------------------------------
 // The caller's arrays are device memory and the call only enqueues: k_dev_check in place of the host's checks
 // and staging, the host batch's size pre-pass and launches, k_gather_reset_soa in place of the gathers, the
-// copy back and the unpacking. Which step runs where, behind what: device_batch_plan
-// (aq_device_batch_plan.h). DevBatchCall is one call's state and one function per step kind -- it orders
-// nothing.
-struct DevBatchCall {
-    aq_ctx* ctx;
-    const DevBatchRings& D;    // ctx->devbatch
-    const DevBatchPlan& plan;
-    std::vector<size_t> off;   // chunk c: rows [off[c], off[c + 1])
+// copy back and the unpacking. Which step runs where, behind what: device_batch_plan (aq_batch_plan.h).
+// DevBatchCall is one call's state and one function per step kind of its own -- it orders nothing.
+struct DevBatchCall : BatchSteps {
+    const DevBatch& D;         // ctx->devbatch
     const aq_device_io& io;
-    double eps;
-    int integrand;
-    static constexpr size_t NP = (size_t)param::nparams;
 
-    int zero(hipStream_t s) {
-        AQ_HIP(hipMemsetAsync(D.cnt, 0, sizeof(unsigned) * 4 * EST_KEYS, s));
-        AQ_HIP(hipMemsetAsync(D.est, 0, sizeof(double) * 2, s));
-        return AQ_OK;
-    }
     int check(int c, hipStream_t s) {
-        const BatchRings::View v = D.at(c, plan.theta);
+        const BatchRings::View v = D.at(c);
         const int m = plan.chunks[c];
         const unsigned blocks = (unsigned)((m + 255) / 256);
         const double *a = io.a + off[c], *b = io.b + off[c];
@@ -1836,31 +1852,9 @@ struct DevBatchCall {
         AQ_HIP(hipGetLastError());
         return AQ_OK;
     }
-    int pre(int c, hipStream_t s) {
-        return size_prepass(ctx, integrand, plan.chunks[c], eps, D.at(c, plan.theta), D.key, plan.preset[c], s);
-    }
-    // (no bounds on the host: plan.first_slot keeps every chunk off the per-CU instance, which takes them as
-    // kernel arguments)
-    int launch_chunk(int c) {
-        const BatchRings::View v = D.at(c, plan.theta);
-        LaunchArgs g;   // (no histograms: hist stays false)
-        g.integrand = integrand;
-        g.k = plan.chunks[c];
-        g.eps = eps;
-        g.max_depth = io.max_depth;
-        g.first_slot = plan.first_slot[c];
-        g.dev_bounds = plan.sorted[c] ? v.sorted : v.bounds;
-        g.dev_theta = plan.sorted[c] ? v.thsorted : v.theta;
-        g.err = plan.err;
-        g.heap = true;
-        ctx->hint.preset = plan.preset[c];
-        const int rc = launch(ctx, g);
-        ctx->hint.preset = false;
-        return rc;
-    }
     // (the kernel returns the slots and their error sums to zero, as gather_clean's two do: they count as clean)
     int gather(int c) {
-        const BatchRings::View v = D.at(c, plan.theta);
+        const BatchRings::View v = D.at(c);
         const int k = plan.chunks[c], first = plan.first_slot[c];
         auto at = [&](auto* p) { return p ? p + off[c] : p; };
         const SoaOut out{at(io.area), (unsigned long long*)at(io.accepted), (unsigned long long*)at(io.tasks),
@@ -1871,9 +1865,7 @@ struct DevBatchCall {
                            (const unsigned*)D.flags(c), io.max_depth ? io.max_depth : AQ_DEFAULT_MAX_DEPTH, out,
                            D.stat.get());
         AQ_HIP(hipGetLastError());
-        if (plan.err) memset(ctx->err_dirty + first, 0, (size_t)k);
-        memset(ctx->dirty + first, 0, (size_t)k);
-        memset(ctx->parts_dirty + first, 0, (size_t)k);
+        mark_clean(ctx, first, k, plan.err);
         return AQ_OK;
     }
 };
@@ -1888,43 +1880,35 @@ int aq_integrate_batch_device(aq_ctx* ctx, size_t n, const aq_device_io* io, dou
     AQ_HIP(hipSetDevice(ctx->device));
     const std::vector<int> chunks = device_batch_chunks(n, device_batch_chunk_rows(env_int("AQ_DEVBATCH_CHUNK", MAXK)));
     const bool sort = env_int("AQ_BATCH_SORT", 1) != 0;
-    // (preset while the workload is fresh: no measured hint for this integrand and tolerance -- batch_run's rule)
-    const bool fresh = ctx->gsplit_env <= 0 && !(ctx->hint.valid && ctx->hint.fid == integrand && ctx->hint.eps == eps &&
-                                                 ctx->hint.nshards == 1);
-    const DevBatchPlan plan = device_batch_plan(chunks, sort, par, err, fresh, stream != nullptr);
+    const BatchPlan plan = device_batch_plan(chunks, sort, par, err, hint_is_fresh(ctx, integrand, eps), stream != nullptr);
     int rc = ctx->devbatch.ensure(par, (size_t)plan.n_events());
     if (rc) return rc;
     if (err && (rc = ensure_err(ctx))) return rc;
     if (!ctx->s_pre) AQ_HIP(ctx->s_pre.create());
-    const hipStream_t streams[] = {ctx->stream, ctx->s_pre, stream ? (hipStream_t)*stream : nullptr};   // by DStream
-    const std::vector<Event>& ev = ctx->devbatch.ev;
-    DevBatchCall call{ctx, ctx->devbatch, plan, std::vector<size_t>(chunks.size() + 1, 0), *io, eps, integrand};
-    for (size_t c = 0; c < chunks.size(); ++c) call.off[c + 1] = call.off[c] + (size_t)chunks[c];
+    // by BStream (no copy streams)
+    const hipStream_t streams[] = {ctx->stream, nullptr, nullptr, ctx->s_pre, stream ? (hipStream_t)*stream : nullptr};
+    DevBatchCall call{BatchSteps(ctx, ctx->devbatch, plan, eps, integrand), ctx->devbatch, *io};
+    call.max_depth = io->max_depth;
     // (a failed step ends the call: what it enqueued so far runs out on its own, and waits for no event that
-    // is never recorded)
-    for (const DevBatchStep& s : plan.steps) {
-        const hipStream_t st = streams[(int)s.stream];
-        for (int w : s.wait)
-            if (w >= 0) AQ_HIP(hipStreamWaitEvent(st, ev[w], 0));
+    // is never recorded -- BatchWalk)
+    return run_plan(plan, streams, ctx->devbatch.ev.data(), [&](const BatchStep& s, hipStream_t st) {
         switch (s.kind) {
-            case DKind::JOIN_IN: case DKind::START: case DKind::FENCE: case DKind::JOIN_OUT: break;   // waits and records
-            case DKind::ZERO: rc = call.zero(st); break;
-            case DKind::CHECK: rc = call.check(s.chunk, st); break;
-            case DKind::PRE: rc = call.pre(s.chunk, st); break;
-            case DKind::LAUNCH: rc = call.launch_chunk(s.chunk); break;
-            case DKind::GATHER: rc = call.gather(s.chunk); break;
+            case BKind::JOIN_IN: case BKind::START: case BKind::FENCE: case BKind::JOIN_OUT: return AQ_OK;   // waits and records
+            case BKind::ZERO: return call.zero(st);
+            case BKind::CHECK: return call.check(s.chunk, st);
+            case BKind::PRE: return call.pre(s.chunk, st);
+            case BKind::LAUNCH: return call.launch_chunk(s.chunk);
+            case BKind::GATHER_SOA: return call.gather(s.chunk);
+            default: return AQ_EINVAL;   // (no such step in a device plan)
         }
-        if (rc) return rc;
-        if (s.record >= 0) AQ_HIP(hipEventRecord(ev[s.record], st));
-    }
-    return AQ_OK;
+    });
 }
 
 int aq_device_batch_check(aq_ctx* ctx, uint64_t* invalid_rows) {
     if (!ctx) return AQ_EINVAL;
     if (invalid_rows) *invalid_rows = 0;
     AQ_HIP(hipSetDevice(ctx->device));
-    const DevBatchRings& D = ctx->devbatch;
+    const DevBatch& D = ctx->devbatch;
     if (!D.stat) {   // no device batch yet
         AQ_HIP(hipStreamSynchronize(ctx->stream));
         return AQ_OK;

@@ -58,6 +58,15 @@ inline std::vector<int> batch_chunks(size_t n, size_t first, size_t last) {
     return c;
 }
 
+// Chunk sizes of an n-row call of the device-resident batch: `chunk` rows each (MAXK, or the AQ_DEVBATCH_CHUNK
+// override clamped to [1, MAXK]), the remainder last. No small first or last chunk: there is no host work to hide.
+inline int device_batch_chunk_rows(long long env) { return (int)std::min<long long>(std::max<long long>(env, 1), MAXK); }
+inline std::vector<int> device_batch_chunks(size_t n, int chunk) {
+    std::vector<int> c;
+    for (size_t done = 0; done < n; done += (size_t)chunk) c.push_back((int)std::min(n - done, (size_t)chunk));
+    return c;
+}
+
 // ---- aq_integrate_batch_tol's rules -------------------------------------------------------------------
 constexpr double TOL_DEFAULT_SHRINK = 8.0;   // err_abs of the trapezoid rule scales as eps^(2/3): a quarter per round
 constexpr int TOL_DEFAULT_ROUNDS = 12;

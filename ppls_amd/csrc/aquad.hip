@@ -980,7 +980,7 @@ __global__ __launch_bounds__(64) void k_gather_err(double* __restrict__ err, int
 // Its two ends, in place of the host batch's staging threads and unpacking threads: k_dev_check before a
 // chunk's size pre-pass and launch, k_gather_reset_soa behind the launch. Both read and write the CALLER's
 // device arrays at the chunk's offset (the host passes the offset pointers); the schedule is
-// aq_device_batch_plan.h's.
+// device_batch_plan's (aq_batch_plan.h).
 constexpr unsigned ROW_INVALID = AQ_ROW_INVALID;
 static_assert(AQ_ROW_TIMEOUT == ERRB_TIMEOUT && AQ_ROW_OVERFLOW == ERRB_OVERFLOW && AQ_ROW_DEPTH == ERRB_DEPTH &&
                   (AQ_ROW_INVALID & (ERRB_TIMEOUT | ERRB_OVERFLOW | ERRB_DEPTH)) == 0,

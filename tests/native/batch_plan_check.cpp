@@ -1,16 +1,19 @@
-// The batch front end's pipeline plan (ppls_amd/csrc/aq_batch_plan.h), g++ alone. Built and run by
-// tests/test_batch_plan.py, which holds the expected schedule and the happens-before check.
-//   --constants     MAXK, PCU_MAXK and BATCH_SORT_MIN as JSON
-//   plan FILE       one "n first last sort theta err fresh" per line -> per case
-//                     case <the line>
-//                     chunks <sizes>
-//                     <kind> <chunk> <stream> <sorted><preset> <waits,|-> <record|-> <uses,|->    per step
-//                     end
-//   walk FILE       one "n first last sort fail code" per line -> the indices of the plan's steps that BatchWalk
-//                   still issues when step `fail` (-1: none) returns `code`, then "rc <the call's code>"
-//                   events print as h2d:c gath:c d2h:c pre:c start zero, uses as r:res:i / w:res:i (i: the
-//                   ring's parity, or the chunk for the pinned regions)
+// The batch pipelines' plans (ppls_amd/csrc/aq_batch_plan.h), g++ alone. Built and run by tests/batch_plan_util.py
+// for tests/test_batch_plan.py and tests/test_device_batch_plan.py, which hold the expected schedules;
+// batch_plan_util holds the happens-before check.
+//   --constants       MAXK, PCU_MAXK, NPARTS and BATCH_SORT_MIN as JSON
+//   chunks N ENV      the chunk sizes of an N-row device-resident call under AQ_DEVBATCH_CHUNK=ENV, as JSON
+//   plan CASE         the case's plan as one line of JSON: chunks, sorted, preset, first_slot, n_events, and per
+//                     step kind, chunk, stream, waits, record and uses [mode, resource, instance] (instance: the
+//                     ring's parity, or the chunk for the regions of the pinned copies and the caller's arrays)
+//   walk CASE         the indices of the plan's steps that BatchWalk still issues when step FAIL (-1: none)
+//                     returns CODE, then "rc <the call's code>"
+//   plan @FILE, walk @FILE     one CASE per line
+// CASE, for plan:     host N FIRST LAST SORT THETA ERR FRESH  |  dev SORT THETA ERR FRESH CALLER SIZE...
+//       for walk:     host N FIRST LAST SORT FAIL CODE        |  dev SORT CALLER FAIL CODE SIZE...
+//                     (a walk's plan has theta rows and error rows and is fresh)
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -19,94 +22,144 @@
 
 using namespace aq;
 
-static const char* const KIND[] = {"start", "fence", "zero", "stage", "h2d", "pre", "launch", "gather", "d2h", "wait",
-                                   "unpack", "drain"};
-static const char* const STREAM[] = {"ctx", "h2d", "d2h", "pre", "host"};
-static const char* const RES[] = {"bounds", "theta", "sorted", "thsorted", "perm", "rows", "errrows", "cnt", "est",
-                                  "key", "slots", "pin_in", "pin_out"};
+static const char* const KIND[] = {"join_in", "start", "fence", "zero", "stage", "h2d", "check", "pre", "launch", "gather",
+                                   "gather_soa", "d2h", "wait", "unpack", "join_out", "drain"};
+static const char* const STREAM[] = {"ctx", "h2d", "d2h", "pre", "caller", "host"};
+static const char* const RES[] = {"bounds", "theta", "flag", "sorted", "thsorted", "perm", "rows", "errrows", "cnt", "est",
+                                  "key", "slots", "pin_in", "pin_out", "in", "out", "invalid", "errbits"};
+static const char* const MODE[] = {"r", "w", "add"};
+// (the event behind a chunk's feed prints as the step that records it: the host's copy, the device's check)
+static const char* const EVENT[2][8] = {{"h2d", "pre", "gath", "d2h", "start", "zero", "in", "out"},
+                                        {"check", "pre", "gath", "d2h", "start", "zero", "in", "out"}};
 
-static std::string event_name(const BatchPlan& p, int e) {
-    if (e < 0) return "-";
-    if (e == p.ev_start()) return "start";
-    if (e == p.ev_zero()) return "zero";
-    static const char* const per_chunk[] = {"h2d", "gath", "d2h", "pre"};
-    return std::string(per_chunk[e % 4]) + ":" + std::to_string(e / 4);
+static std::string event_name(const BatchPlan& p, bool dev, int e) {
+    const int c = e / p.per_chunk;
+    if (c < p.nc()) return std::string(EVENT[dev][e % p.per_chunk]) + ":" + std::to_string(c);
+    return EVENT[dev][(int)BEv::START + e - p.per_chunk * p.nc()];
 }
 
-static void print_plan(const BatchPlan& p) {
-    printf("chunks");
-    for (int m : p.chunks) printf(" %d", m);
-    printf("\n");
+static void print_ints(const char* name, const std::vector<int>& v) {
+    printf("\"%s\": [", name);
+    for (size_t i = 0; i < v.size(); ++i) printf("%s%d", i ? ", " : "", v[i]);
+    printf("]");
+}
+
+static void print_plan(const BatchPlan& p, bool dev) {
+    printf("{");
+    print_ints("chunks", p.chunks);
+    printf(", ");
+    print_ints("sorted", std::vector<int>(p.sorted.begin(), p.sorted.end()));
+    printf(", ");
+    print_ints("preset", std::vector<int>(p.preset.begin(), p.preset.end()));
+    printf(", ");
+    print_ints("first_slot", p.first_slot);
+    printf(", \"n_events\": %d, \"steps\": [", p.n_events());
+    bool first_step = true;
     for (const BatchStep& s : p.steps) {
-        const bool of_chunk = s.chunk >= 0;
-        printf("%s %d %s %d%d ", KIND[(int)s.kind], s.chunk, STREAM[(int)s.stream], of_chunk && p.sorted[s.chunk] ? 1 : 0,
-               of_chunk && p.preset[s.chunk] ? 1 : 0);
-        std::string waits;
+        printf("%s{\"kind\": \"%s\", \"chunk\": %d, \"stream\": \"%s\", \"waits\": [", first_step ? "" : ", ",
+               KIND[(int)s.kind], s.chunk, STREAM[(int)s.stream]);
+        first_step = false;
+        bool sep = false;
         for (int w : s.wait)
-            if (w >= 0) waits += (waits.empty() ? "" : ",") + event_name(p, w);
-        printf("%s %s ", waits.empty() ? "-" : waits.c_str(), event_name(p, s.record).c_str());
-        std::string uses;
+            if (w >= 0) printf("%s\"%s\"", sep ? ", " : "", event_name(p, dev, w).c_str()), sep = true;
+        printf("], \"record\": ");
+        if (s.record >= 0) printf("\"%s\"", event_name(p, dev, s.record).c_str());
+        else printf("null");
+        printf(", \"uses\": [");
+        sep = false;
         for (const BatchUse& u : BATCH_USES) {
-            if (!batch_use_applies(p, s, u)) continue;
+            if (!use_applies(p, s, u)) continue;
             const int own = s.chunk & 1;
-            int inst[2] = {0, -1};
+            std::vector<int> inst;
             switch (u.which) {
-                case BWhich::OWN: inst[0] = own; break;
-                case BWhich::OTHER: inst[0] = own ^ 1; break;
-                case BWhich::BOTH: inst[1] = 1; break;
-                case BWhich::ONE: break;
-                case BWhich::CHUNK: inst[0] = s.chunk; break;
+                case BWhich::OWN: inst = {own}; break;
+                case BWhich::OTHER: inst = {own ^ 1}; break;
+                case BWhich::BOTH: inst = {0, 1}; break;
+                case BWhich::ONE: inst = {0}; break;
+                case BWhich::CHUNK: inst = {s.chunk}; break;
+                case BWhich::ALL:
+                    for (int c = 0; c < p.nc(); ++c) inst.push_back(c);
+                    break;
             }
-            for (int i : inst)
-                if (i >= 0)
-                    uses += (uses.empty() ? "" : ",") + std::string(u.write ? "w:" : "r:") + RES[(int)u.res] + ":" +
-                            std::to_string(i);
+            for (int i : inst) printf("%s[\"%s\", \"%s\", %d]", sep ? ", " : "", MODE[(int)u.mode], RES[(int)u.res], i), sep = true;
         }
-        printf("%s\n", uses.empty() ? "-" : uses.c_str());
+        printf("]}");
     }
-    printf("end\n");
+    printf("]}\n");
+}
+
+// one CASE (above), already split into words; false: not a case
+static bool run_case(bool walk, const std::vector<std::string>& w) {
+    if (w.empty()) return false;
+    const bool dev = w[0] == "dev";
+    if (!dev && w[0] != "host") return false;
+    std::vector<long long> v;
+    for (size_t i = 1; i < w.size(); ++i) v.push_back(atoll(w[i].c_str()));
+    if (dev ? v.size() < (walk ? 4u : 5u) : v.size() != (walk ? 6u : 7u)) return false;
+    BatchPlan p;
+    if (dev) {
+        const std::vector<int> chunks(v.begin() + (walk ? 4 : 5), v.end());
+        p = walk ? device_batch_plan(chunks, v[0] != 0, true, true, true, v[1] != 0)
+                 : device_batch_plan(chunks, v[0] != 0, v[1] != 0, v[2] != 0, v[3] != 0, v[4] != 0);
+    } else {
+        const std::vector<int> chunks = batch_chunks((size_t)v[0], (size_t)v[1], (size_t)v[2]);
+        p = walk ? batch_plan(chunks, v[3] != 0, true, true, true) : batch_plan(chunks, v[3] != 0, v[4] != 0, v[5] != 0, v[6] != 0);
+    }
+    if (!walk) {
+        print_plan(p, dev);
+        return true;
+    }
+    const long long fail = v[dev ? 2 : 4], code = v[dev ? 3 : 5];
+    BatchWalk bw;
+    for (size_t i = 0; i < p.steps.size(); ++i) {
+        if (!bw.runs(p.steps[i])) continue;
+        printf("%zu ", i);
+        bw.done(p.steps[i], (long long)i == fail ? (int)code : 0);
+    }
+    printf("rc %d\n", bw.rc);
+    return true;
+}
+
+static std::vector<std::string> words(const char* line) {
+    std::vector<std::string> w;
+    for (const char* s = line; *s;) {
+        const size_t n = strcspn(s, " \t\r\n");
+        if (n) w.emplace_back(s, n);
+        s += n + (s[n] ? 1 : 0);
+    }
+    return w;
 }
 
 int main(int argc, char** argv) {
-    static_assert(sizeof(KIND) / sizeof(*KIND) == (size_t)BKind::DRAIN + 1 && sizeof(RES) / sizeof(*RES) == (size_t)BRes::PIN_OUT + 1 &&
-                      sizeof(STREAM) / sizeof(*STREAM) == (size_t)BStream::HOST + 1,
+    static_assert(sizeof(KIND) / sizeof(*KIND) == (size_t)BKind::DRAIN + 1 && sizeof(RES) / sizeof(*RES) == (size_t)BRes::ERRBITS + 1 &&
+                      sizeof(STREAM) / sizeof(*STREAM) == (size_t)BStream::HOST + 1 && sizeof(MODE) / sizeof(*MODE) == (size_t)BMode::ADD + 1 &&
+                      sizeof(EVENT[0]) / sizeof(*EVENT[0]) == (size_t)BEv::OUT + 1,
                   "one name per enumerator");
     if (argc == 2 && !strcmp(argv[1], "--constants")) {
-        printf("{\"MAXK\": %d, \"PCU_MAXK\": %d, \"BATCH_SORT_MIN\": %d}\n", MAXK, PCU_MAXK, BATCH_SORT_MIN);
+        printf("{\"MAXK\": %d, \"PCU_MAXK\": %d, \"NPARTS\": %d, \"BATCH_SORT_MIN\": %d}\n", MAXK, PCU_MAXK, NPARTS, BATCH_SORT_MIN);
         return 0;
     }
-    const bool walk = argc == 3 && !strcmp(argv[1], "walk");
-    FILE* f = argc == 3 && (walk || !strcmp(argv[1], "plan")) ? fopen(argv[2], "r") : nullptr;
-    if (!f) {
-        fprintf(stderr, "usage: batch_plan_check --constants | plan FILE | walk FILE\n");
-        return 2;
+    if (argc == 4 && !strcmp(argv[1], "chunks")) {
+        printf("{");
+        print_ints("chunks", device_batch_chunks((size_t)strtoull(argv[2], nullptr, 10), device_batch_chunk_rows(atoll(argv[3]))));
+        printf("}\n");
+        return 0;
     }
-    int rows = 0;
-    unsigned long long n, first, last;
-    int sort, theta, err, fresh;
-    int fail, code;
-    while (walk && fscanf(f, "%llu %llu %llu %d %d %d", &n, &first, &last, &sort, &fail, &code) == 6) {
-        ++rows;
-        const BatchPlan p = batch_plan(batch_chunks((size_t)n, (size_t)first, (size_t)last), sort != 0, true, true, true);
-        BatchWalk w;
-        for (size_t i = 0; i < p.steps.size(); ++i) {
-            if (!w.runs(p.steps[i])) continue;
-            printf("%zu ", i);
-            w.done(p.steps[i], (int)i == fail ? code : 0);
+    const bool walk = argc >= 3 && !strcmp(argv[1], "walk");
+    if (argc >= 3 && (walk || !strcmp(argv[1], "plan"))) {
+        if (argv[2][0] != '@') {
+            if (run_case(walk, std::vector<std::string>(argv + 2, argv + argc))) return 0;
+        } else if (FILE* f = argc == 3 ? fopen(argv[2] + 1, "r") : nullptr) {
+            int rows = 0;
+            char line[4096];
+            bool ok = true;
+            while (ok && fgets(line, sizeof line, f)) ok = run_case(walk, words(line)), rows += ok;
+            fclose(f);
+            if (ok && rows) return 0;
+            fprintf(stderr, "unreadable row after %d rows\n", rows);
+            return 2;
         }
-        printf("rc %d\n", w.rc);
     }
-    while (!walk && fscanf(f, "%llu %llu %llu %d %d %d %d", &n, &first, &last, &sort, &theta, &err, &fresh) == 7) {
-        ++rows;
-        printf("case %llu %llu %llu %d %d %d %d\n", n, first, last, sort, theta, err, fresh);
-        const std::vector<int> chunks = batch_chunks((size_t)n, (size_t)first, (size_t)last);
-        print_plan(batch_plan(chunks, sort != 0, theta != 0, err != 0, fresh != 0));
-    }
-    const bool eof = feof(f) != 0;
-    fclose(f);
-    if (!eof || !rows) {
-        fprintf(stderr, "unreadable row after %d rows\n", rows);
-        return 2;
-    }
-    return 0;
+    fprintf(stderr, "usage: batch_plan_check --constants | chunks N ENV | plan CASE | plan @FILE | walk CASE | walk @FILE\n");
+    return 2;
 }

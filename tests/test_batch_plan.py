@@ -1,74 +1,30 @@
-"""The batch front end's pipeline plan (`ppls_amd/csrc/aq_batch_plan.h`, what `batch_run` walks) built alone
-with g++, plain and under AddressSanitizer + UBSan: (a) the plan against a restatement of the schedule, two
-step lists pinned by hand; (b) a happens-before check over the printed plan and its resource table -- every two
-steps that touch the same buffer, one of them writing, are ordered -- which must report a hazard when any
-needed wait is dropped, and none for the one wait the host's own synchronisation implies."""
+"""The batch front end's pipeline plan (`batch_plan` of `ppls_amd/csrc/aq_batch_plan.h`, what `batch_run` walks)
+built alone with g++, plain and under AddressSanitizer + UBSan: (a) the plan against a restatement of the schedule,
+two step lists pinned by hand; (b) a happens-before check over the printed plan and its resource table
+(batch_plan_util.hazards) -- every two steps that touch the same buffer, one of them writing, are ordered -- which
+must report a hazard when any needed wait is dropped, and none for the one wait the host's own synchronisation
+implies."""
 import itertools
 import json
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "batch_plan_check.cpp")
-INC = [os.path.join(ROOT, "ppls_amd", "csrc"), os.path.join(ROOT, "include")]
-SAN = [None, "address,undefined"]
-MAXK = 262144
+from batch_plan_util import MAXK, SAN, brief as _brief, exe as _exe, hazards as _hazards, run as _run, run_cases
+
 GRID = list(itertools.product([1, 63, 64, 200, 468, 1000, 3000, MAXK + 1, 2 * MAXK + 1000, 1000003, 5 * MAXK + 7],
                               [0, 16, 32, 64, 1024, 131072], [0, 20, 4096], [1, 0]))
 
 
-def _exe(san, tmp_path):
-    exe = str(tmp_path / "batch_plan_check")
-    if os.path.exists(exe):
-        return exe
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-I", INC[0], "-I", INC[1], SRC, "-o", exe]
-    if san:
-        cmd.insert(1, "-fsanitize=" + san)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode and san:
-        pytest.skip("sanitizer runtime unavailable: " + r.stderr[-400:])
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-def _run(san, tmp_path, *args):
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([_exe(san, tmp_path), *args], capture_output=True, text=True, timeout=120, env=env)
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout
-
-
-def _plans(san, tmp_path, cases, theta=1, err=1, fresh=1):
+def _plans(exe, tmp_path, cases, theta=1, err=1, fresh=1):
     """{(n, first, last, sort): (chunks, steps)}; a step is a dict of kind, chunk, stream, sorted, preset, waits,
-    record and uses [(write, resource, instance)]."""
-    path = tmp_path / "cases.txt"
-    path.write_text("".join(f"{n} {first} {last} {sort} {theta} {err} {fresh}\n" for n, first, last, sort in cases))
-    out, it = {}, iter(_run(san, tmp_path, "plan", str(path)).splitlines())
-    for case in cases:
-        assert next(it).split() == ["case"] + [str(x) for x in case] + [str(theta), str(err), str(fresh)]
-        chunks = [int(x) for x in next(it).split()[1:]]
-        steps = []
-        for ln in it:
-            if ln == "end":
-                break
-            kind, chunk, stream, flags, waits, record, uses = ln.split()
-            steps.append(dict(kind=kind, chunk=int(chunk), stream=stream, sorted=flags[0] == "1", preset=flags[1] == "1",
-                              waits=() if waits == "-" else tuple(waits.split(",")), record=None if record == "-" else record,
-                              uses=[] if uses == "-" else [(u[0] == "w", u.split(":")[1], int(u.split(":")[2]))
-                                                           for u in uses.split(",")]))
-        out[case] = (chunks, steps)
-    assert next(it, None) is None
+    record and uses [[mode, resource, instance]]."""
+    out = {}
+    for case, p in zip(cases, run_cases(exe, "plan", [("host",) + case + (theta, err, fresh) for case in cases], tmp_path)):
+        assert p["first_slot"] == [0] * len(p["chunks"]) and p["n_events"] == 4 * len(p["chunks"]) + 2
+        for s in p["steps"]:
+            s["sorted"], s["preset"] = (bool(s["chunk"] >= 0 and p[k][s["chunk"]]) for k in ("sorted", "preset"))
+        out[case] = (p["chunks"], p["steps"])
     return out
-
-
-def _brief(steps):
-    return [(s["kind"], s["chunk"], s["stream"], s["waits"], s["record"]) for s in steps]
 
 
 def _chunks_rule(n, first, last):
@@ -118,46 +74,12 @@ def _schedule(chunks, sort):
     return srt, steps
 
 
-def _hazards(steps, drop=lambda step, event: False):
-    """Pairs of steps that conflict on a buffer and are not ordered. Order: steps of one stream (the host is one)
-    follow each other; a wait puts the step behind the one that recorded the event; a device step follows the
-    last host step issued before it; the drain follows everything. `drop(step, event)`: leave that wait out."""
-    before, last_on, recorded, last_host = [], {}, {}, None
-    for i, s in enumerate(steps):
-        preds = [last_on.get(s["stream"])]
-        preds += [recorded[e] for e in s["waits"] if not drop(s, e)]   # (KeyError: a wait for an event never recorded)
-        if s["stream"] != "host":
-            preds.append(last_host)
-        if s["kind"] == "drain":
-            preds += range(i)
-        m = 0
-        for p in preds:
-            if p is not None:
-                m |= before[p] | (1 << p)
-        before.append(m)
-        last_on[s["stream"]] = i
-        if s["stream"] == "host":
-            last_host = i
-        if s["record"]:
-            assert s["record"] not in recorded, s
-            recorded[s["record"]] = i
-    out = []
-    for j, t in enumerate(steps):
-        for i in range(j):
-            if before[j] >> i & 1:
-                continue
-            for wi, ri, ii in steps[i]["uses"]:
-                for wj, rj, ij in t["uses"]:
-                    if (wi or wj) and (ri, ii) == (rj, ij):
-                        out.append((steps[i]["kind"], steps[i]["chunk"], t["kind"], t["chunk"], ri, ii))
-    return out
-
-
 @pytest.mark.parametrize("san", SAN)
-def test_plan_is_todays_schedule(tmp_path, san):
-    k = json.loads(_run(san, tmp_path, "--constants"))
-    assert k == {"MAXK": MAXK, "PCU_MAXK": 12, "BATCH_SORT_MIN": 64}
-    plans = _plans(san, tmp_path, GRID)
+def test_plan_is_todays_schedule(tmp_path, tmp_path_factory, san):
+    exe = _exe(san, tmp_path_factory)
+    k = json.loads(_run(exe, "--constants"))
+    assert k == {"MAXK": MAXK, "PCU_MAXK": 12, "NPARTS": 16384, "BATCH_SORT_MIN": 64}
+    plans = _plans(exe, tmp_path, GRID)
     assert len(plans) == 396
     for (n, first, last, sort), (chunks, steps) in plans.items():
         assert chunks == _chunks_rule(n, first, last), (n, first, last)
@@ -206,10 +128,10 @@ def test_plan_is_todays_schedule(tmp_path, san):
         ("drain", -1, "host", (), None), ("unpack", 3, "host", (), None)]
     assert [s["preset"] for s in steps if s["kind"] == "pre"] == [True, False, False]
     launch3 = next(s for s in steps if (s["kind"], s["chunk"]) == ("launch", 3))
-    assert sorted(launch3["uses"]) == [(False, "bounds", 1), (False, "theta", 1), (True, "slots", 0)]
+    assert sorted(launch3["uses"]) == [["r", "bounds", 1], ["r", "theta", 1], ["w", "slots", 0]]
     # the resource table's conditions: without theta and error rows nothing names their rings; a context that
     # holds a measured hint presets nothing
-    _, bare = _plans(san, tmp_path, [(468, 64, 0, 1)], theta=0, err=0, fresh=0)[(468, 64, 0, 1)]
+    _, bare = _plans(exe, tmp_path, [(468, 64, 0, 1)], theta=0, err=0, fresh=0)[(468, 64, 0, 1)]
     assert _brief(bare) == _brief(steps) and not any(s["preset"] for s in bare)
     assert {r for s in steps for _, r, _ in s["uses"]} - {r for s in bare for _, r, _ in s["uses"]} == \
         {"theta", "thsorted", "errrows"}
@@ -263,11 +185,12 @@ def _issued_before_the_plan(chunks, sort, fail, code):
 
 
 @pytest.mark.parametrize("san", SAN)
-def test_a_failed_step_leaves_out_what_it_did_before(tmp_path, san):
+def test_a_failed_step_leaves_out_what_it_did_before(tmp_path, tmp_path_factory, san):
     """BatchWalk (what batch_run asks before every step) against the control flow batch_run had: every step of
     three plans failing in turn, with a bad bound's code for the staging and a device error's for the rest."""
+    exe = _exe(san, tmp_path_factory)
     cases = [(468, 64, 0, 1), (200, 32, 0, 1), (3000, 1024, 20, 0), (63, 0, 0, 1)]
-    plans = _plans(san, tmp_path, cases)
+    plans = _plans(exe, tmp_path, cases)
     rows, want = [], []
     for case in cases:
         chunks, steps = plans[case]
@@ -276,23 +199,17 @@ def test_a_failed_step_leaves_out_what_it_did_before(tmp_path, san):
             if kind in ("unpack", "drain"):   # (the host's unpacking returns nothing; a failed drain fails the call,
                 continue                      # below)
             code = -1 if kind == "stage" else -2
-            rows.append(case + (f, code))
+            rows.append(("host",) + case + (f, code))
             issued, rc = _issued_before_the_plan(chunks, case[3], (kind, steps[f]["chunk"]) if f >= 0 else None, code)
             want.append(([i for i, s in enumerate(steps) if (s["kind"], s["chunk"]) in issued], rc))   # (in plan order)
-    path = tmp_path / "walk.txt"
-    path.write_text("".join(" ".join(str(x) for x in r) + "\n" for r in rows))
-    got = []
-    for ln in _run(san, tmp_path, "walk", str(path)).splitlines():
-        idx, rc = ln.split("rc")
-        got.append(([int(x) for x in idx.split()], int(rc)))
+    got = run_cases(exe, "walk", rows, tmp_path)
     assert len(got) == len(rows) and len(rows) > len(cases)
     for r, g, w in zip(rows, got, want):
         assert g == w, (r, g, w)
     # a failing drain fails a call that had succeeded so far, and the last chunk is then not unpacked
     chunks, steps = plans[(468, 64, 0, 1)]
     drain = next(i for i, s in enumerate(steps) if s["kind"] == "drain")
-    path.write_text(f"468 64 0 1 {drain} -2\n")
-    assert _run(san, tmp_path, "walk", str(path)).split() == [str(i) for i in range(drain + 1)] + ["rc", "-2"]
+    assert _run(exe, "walk", "host", 468, 64, 0, 1, drain, -2).split() == [str(i) for i in range(drain + 1)] + ["rc", "-2"]
 
 
 # every wait the schedule needs: (what is dropped, a case that shows it); chunk numbers by the step's own
@@ -309,8 +226,8 @@ MUTATIONS = [
 
 
 @pytest.mark.parametrize("san", SAN)
-def test_every_ring_reuse_is_ordered(tmp_path, san):
-    plans = _plans(san, tmp_path, GRID)
+def test_every_ring_reuse_is_ordered(tmp_path, tmp_path_factory, san):
+    plans = _plans(_exe(san, tmp_path_factory), tmp_path, GRID)
     for case, (_, steps) in plans.items():
         assert _hazards(steps) == [], case
     for what, drop, case in MUTATIONS:

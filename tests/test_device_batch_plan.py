@@ -1,44 +1,33 @@
-"""The device-resident batch's pipeline plan (`ppls_amd/csrc/aq_device_batch_plan.h`, what
-`aq_integrate_batch_device` walks) built alone with g++: (a) the chunking and the plan against a restatement of
-the schedule; (b) a happens-before check over the plan and its resource table -- every two steps that touch the
-same buffer, one of them writing, are ordered by streams and event waits -- which must report a hazard when any
-needed wait is dropped; (c) no step is the host's, launches and gathers run on the context's stream, and a chunk
-of fewer than PCU_MAXK rows is launched into slots from NPARTS."""
+"""The device-resident batch's pipeline plan (`device_batch_plan` of `ppls_amd/csrc/aq_batch_plan.h`, what
+`aq_integrate_batch_device` walks) built alone with g++, plain and under AddressSanitizer + UBSan: (a) the chunking
+and the plan against a restatement of the schedule; (b) a happens-before check over the plan and its resource
+table (batch_plan_util.hazards) -- every two steps that touch the same buffer, one of them writing, are ordered by
+streams and event waits -- which must report a hazard when any needed wait is dropped; (c) no step is the host's,
+launches and gathers run on the context's stream, and a chunk of fewer than PCU_MAXK rows is launched into slots
+from NPARTS; (d) a failed step ends the call there."""
 import itertools
 import json
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "device_batch_plan_check.cpp")
-INC = [os.path.join(ROOT, "ppls_amd", "csrc"), os.path.join(ROOT, "include")]
-MAXK = 262144
+import batch_plan_util
+from batch_plan_util import MAXK, SAN, hazards as _hazards, run_cases
+
 CHUNKS = [[5], [100], [100, 100, 5], [64] * 5]
 FLAGS = list(itertools.product([1, 0], [0, 1], [0, 1], [1, 0]))   # sort, theta, err, caller
 
 
-@pytest.fixture(scope="module")
+@pytest.fixture
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("devplan") / "device_batch_plan_check")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-I", INC[0], "-I", INC[1], SRC, "-o", out],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out
+    return batch_plan_util.exe(None, tmp_path_factory)   # (test_under_the_sanitizers: the same tests, that build)
 
 
 def _json(exe, *args):
-    r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout)
+    return json.loads(batch_plan_util.run(exe, *args))
 
 
 def _plan(exe, chunks, sort, theta, err, caller, fresh=1):
-    return _json(exe, "plan", sort, theta, err, fresh, caller, *chunks)
+    return _json(exe, "plan", "dev", sort, theta, err, fresh, caller, *chunks)
 
 
 def _schedule(chunks, sort, caller):
@@ -64,41 +53,12 @@ def _schedule(chunks, sort, caller):
     feed(0)
     for c in range(nc):
         steps.append(("launch", c, "ctx", [f"pre:{c}" if srt[c] else f"check:{c}"], None))
-        steps.append(("gather", c, "ctx", [], f"gath:{c}" if c + 1 < nc else ("out" if caller else None)))
+        steps.append(("gather_soa", c, "ctx", [], f"gath:{c}" if c + 1 < nc else ("out" if caller else None)))
         if c + 1 < nc:
             feed(c + 1)
     if caller:
         steps.append(("join_out", -1, "caller", ["out"], None))
     return srt, steps
-
-
-def _hazards(steps, drop=lambda step, event: False):
-    """Pairs of steps that conflict on a buffer and are not ordered. Order: the steps of one stream follow each
-    other; a wait puts the step behind the one that recorded the event (and all before that). Two atomic adds
-    commute. `drop(step, event)`: leave that wait out."""
-    before, last_on, recorded = [], {}, {}
-    for i, s in enumerate(steps):
-        preds = [last_on.get(s["stream"])]
-        preds += [recorded[e] for e in s["waits"] if not drop(s, e)]   # (KeyError: a wait for an event never recorded)
-        m = 0
-        for p in preds:
-            if p is not None:
-                m |= before[p] | (1 << p)
-        before.append(m)
-        last_on[s["stream"]] = i
-        if s["record"]:
-            assert s["record"] not in recorded, s
-            recorded[s["record"]] = i
-    out = []
-    for j, t in enumerate(steps):
-        for i in range(j):
-            if before[j] >> i & 1:
-                continue
-            for mi, ri, ii in steps[i]["uses"]:
-                for mj, rj, ij in t["uses"]:
-                    if (ri, ii) == (rj, ij) and not (mi == "r" and mj == "r") and not (mi == "add" and mj == "add"):
-                        out.append((steps[i]["kind"], steps[i]["chunk"], t["kind"], t["chunk"], ri, ii))
-    return out
 
 
 def test_chunks_are_full_launches_and_a_remainder(exe):
@@ -136,15 +96,15 @@ def test_no_host_step_and_launches_on_the_context_stream(exe):
         for sort, theta, err, caller in FLAGS:
             steps = _plan(exe, chunks, sort, theta, err, caller)["steps"]
             assert {s["stream"] for s in steps} <= {"ctx", "pre", "caller"}   # (no host stream exists in the plan)
-            assert {s["kind"] for s in steps} <= {"join_in", "start", "fence", "zero", "check", "pre", "launch", "gather",
-                                                  "join_out"}
+            assert {s["kind"] for s in steps} <= {"join_in", "start", "fence", "zero", "check", "pre", "launch",
+                                                  "gather_soa", "join_out"}
             for s in steps:
-                if s["kind"] in ("launch", "gather"):
+                if s["kind"] in ("launch", "gather_soa"):
                     assert s["stream"] == "ctx"
                 if s["kind"] in ("join_in", "join_out"):
                     assert s["stream"] == "caller" and caller
             assert [s["chunk"] for s in steps if s["kind"] == "launch"] == list(range(len(chunks)))
-            assert [s["chunk"] for s in steps if s["kind"] == "gather"] == list(range(len(chunks)))
+            assert [s["chunk"] for s in steps if s["kind"] == "gather_soa"] == list(range(len(chunks)))
             # chunk c + 1's check is enqueued on the side stream, with no wait for chunk c's launch or gather
             for s in steps:
                 if s["kind"] in ("check", "pre") and s["chunk"] > 0:
@@ -161,7 +121,7 @@ def test_resource_table_conditions(exe):
     assert sorted(launch2["uses"]) == [["r", "bounds", 0], ["r", "theta", 0], ["w", "slots", 0]]
     launch1 = next(s for s in full if (s["kind"], s["chunk"]) == ("launch", 1))
     assert sorted(launch1["uses"]) == [["r", "sorted", 1], ["r", "thsorted", 1], ["w", "slots", 0]]
-    gather1 = next(s for s in full if (s["kind"], s["chunk"]) == ("gather", 1))
+    gather1 = next(s for s in full if (s["kind"], s["chunk"]) == ("gather_soa", 1))
     assert sorted(gather1["uses"]) == [["add", "errbits", 0], ["r", "flag", 1], ["r", "perm", 1], ["w", "out", 1],
                                        ["w", "slots", 0]]
     join_out = full[-1]
@@ -196,4 +156,33 @@ def test_every_ring_reuse_is_ordered(exe):
     # a ring parity is reused: chunk 2's check writes what chunk 0's launch and gather read
     steps = _plan(exe, [64] * 5, 1, 1, 1, 1)["steps"]
     haz = _hazards(steps, lambda s, e: s["kind"] == "check" and e.startswith("gath:"))
-    assert ("gather", 0, "check", 2, "flag", 0) in haz and ("launch", 1, "pre", 3, "sorted", 1) in haz
+    assert ("gather_soa", 0, "check", 2, "flag", 0) in haz and ("launch", 1, "pre", 3, "sorted", 1) in haz
+
+
+@pytest.mark.parametrize("san", SAN)
+def test_a_failed_step_ends_the_call_there(san, tmp_path_factory, tmp_path):
+    """BatchWalk over the device plans: with each step failing in turn the steps issued are exactly those up to
+    and including it -- nothing enqueued waits for an event that is never recorded, and the caller's stream is not
+    joined behind a failed call -- and the call returns that step's code; with no failure every step is issued."""
+    exe = batch_plan_util.exe(san, tmp_path_factory)
+    rows, want = [], []
+    for chunks, caller, sort in itertools.product(CHUNKS, [0, 1], [0, 1]):
+        steps = _plan(exe, chunks, sort, 1, 1, caller)["steps"]
+        assert steps[-1]["kind"] == ("join_out" if caller else "gather_soa")
+        for f in range(-1, len(steps)):
+            code = -3 - f % 5
+            rows.append(("dev", sort, caller, f, code, *chunks))
+            want.append((list(range(f + 1)), code) if f >= 0 else (list(range(len(steps))), 0))
+    got = run_cases(exe, "walk", rows, tmp_path)
+    assert len(got) == len(rows) and len(rows) > 16 * 4
+    for r, g, w in zip(rows, got, want):
+        assert g == w, (r, g, w)
+
+
+@pytest.mark.parametrize("san", SAN[1:])
+@pytest.mark.parametrize("test", [test_chunks_are_full_launches_and_a_remainder, test_plan_is_the_stated_schedule,
+                                  test_no_host_step_and_launches_on_the_context_stream, test_resource_table_conditions,
+                                  test_every_ring_reuse_is_ordered], ids=lambda t: t.__name__)
+def test_under_the_sanitizers(test, san, tmp_path_factory):
+    """Every test above once more, on the check program built with -fsanitize (as the host plans' tests are)."""
+    test(batch_plan_util.exe(san, tmp_path_factory))
