@@ -449,8 +449,29 @@ int aq_device_batch_check(aq_ctx *ctx, uint64_t *invalid_rows);
  * equal to cum_k at every node x_k, k < m (at x_m: cum_m-1 plus the last panel's trapezoid), its error on a full leaf the leaf's accepted |d| <= EPSILON. A q outside
  * [x_0, x_m], or NaN, gives NaN. The call only enqueues on the context's stream and reads nothing on the host
  * (aq_synchronize orders the output). AQ_EINVAL: a NULL ctx, a NULL array with nq > 0, n_nodes < 3.
+ * aq_mesh_invert answers the reverse question, for each y of d_y[nq] the x at which the integral from x_0 reaches
+ * y: quantiles, equal-mass partitions, inverse-CDF samples. For a mesh whose cum is non-decreasing (F >= 0, or
+ * any F whose trapezoids are all >= 0) and cum_0 <= y <= cum_m, with k the largest index <= m - 1 such that
+ * cum_k <= y, one IEEE double operation each, nothing contracted, sqrt correctly rounded:
+ *   w = x_k+1 - x_k;  r = y - cum_k;  s = (f_k+1 - f_k) / w;
+ *   disc = fmax(f_k * f_k + (2 * s) * r, 0);  den = f_k + sqrt(disc);
+ *   h = (r == 0) ? 0 : (2 * r) / den;  h = fmin(h, w);  out = x_k + h
+ * -- the stable root of r = f_k h + s h^2 / 2, which inverts aq_mesh_eval's trapezoid on the partial panel. So:
+ * out lies in [x_k, x_k+1]; out is non-decreasing in y; out == x_k exactly when y == cum_k (for k < m, where cum
+ * increases strictly); across a run of equal cum values (panels of zero area) the answer is the right end of the
+ * run; at y == cum_m the answer is the last panel's root (b up to the conditioning ulp(y) / F), or x_m-1 if that
+ * panel has zero area. A y outside [cum_0, cum_m], or NaN, gives NaN. If the panel the search ends in does not
+ * satisfy cum_k <= y <= cum_k+1 the output is NaN: that happens only when cum is not non-decreasing -- F changes
+ * sign, as sin(1/x) does -- and on such a mesh every output is NaN or a point of [x_0, x_m] and nothing more is
+ * promised (every index stays in bounds). The call only enqueues on the context's stream, reads nothing on the
+ * host and owns no device memory (aq_synchronize orders the output). AQ_EINVAL as for aq_mesh_eval: a NULL ctx,
+ * a NULL array with nq > 0, n_nodes < 3; nq == 0 enqueues nothing. Few queries take a binary search over cum, one
+ * query per lane; many (2^21 and more) a kernel that first searches every 2^sh-th value of cum in a 2048-entry
+ * table in LDS; both return the same k, and AQ_MESH_INVERT=0 / 1 in the environment, read per call, forces the
+ * first / the second.
  * Not covered: meshes from the persistent kernel (aq_integrate*, shards, aq_group, the batches, the
- * tolerance-driven batch), AQ_F_PARAM, several meshes per call, host-memory outputs (callers copy), the CLI. */
+ * tolerance-driven batch), AQ_F_PARAM, several meshes per call (aq_mesh_eval and aq_mesh_invert alike), inversion
+ * of non-monotone meshes, host-memory outputs (callers copy), the CLI. */
 typedef struct {
     double  *x;      /* DEVICE [cap_nodes]: x_0 = a < x_1 < ... < x_m = b, m = 2 * accepted */
     double  *f;      /* DEVICE [cap_nodes]: F(x_k), the values the tree evaluated */
@@ -461,10 +482,12 @@ int aq_integrate_mesh(aq_ctx *ctx, const aq_problem *p, uint32_t frontier_cap, i
                       uint64_t cap_nodes, const aq_mesh_io *io, aq_result *res, uint64_t *n_nodes);
 int aq_mesh_eval(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const double *d_f, const double *d_cum,
                  size_t nq, const double *d_q, double *d_out);
+int aq_mesh_invert(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const double *d_f, const double *d_cum,
+                   size_t nq, const double *d_y, double *d_out);
 
 /* ---- measurement ----------------------------------------------------------------------------
- * When enabled, HIP events bracket every launch of the persistent kernel on the context's
- * stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */
+ * When enabled, HIP events bracket every launch of the persistent kernel, and of aq_mesh_invert's kernel, on
+ * the context's stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */
 int aq_kernel_timing(aq_ctx *ctx, int enable);
 int aq_kernel_time(aq_ctx *ctx, double *total_ms, uint64_t *launches);
 /* Per-workgroup timeline of the persistent kernel (48 uint64 words per workgroup: realtime stamps

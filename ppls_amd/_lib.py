@@ -25,7 +25,7 @@ EXPORTS = (
     "aq_err_extrapolate", "aq_integrate_err", "aq_integrate_many_err_async", "aq_fetch_err", "aq_integrate_batch_err",
     "aq_integrate_batch_tol",
     "aq_integrate_batch_device", "aq_device_batch_check",
-    "aq_integrate_mesh", "aq_mesh_eval",
+    "aq_integrate_mesh", "aq_mesh_eval", "aq_mesh_invert",
 )
 
 AQ_MAX_LEVELS = 128
@@ -161,6 +161,7 @@ def load(build_if_missing=True):
         "aq_device_batch_check": ([vp, up], c_int),
         "aq_integrate_mesh": ([vp, P, ctypes.c_uint32, c_int, ctypes.c_uint64, ctypes.POINTER(aq_mesh_io), R, up], c_int),
         "aq_mesh_eval": ([vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
+        "aq_mesh_invert": ([vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -538,11 +538,8 @@ class Context:
         m = int(n.value)
         return self._result(r), x[:m], f[:m], cum[:m], level[:m - 1]
 
-    def mesh_eval(self, x, f, cum, q):
-        """The integral from x[0] to every q on a mesh of integrate_mesh (aq_mesh_eval: the trapezoid rule on the
-        partial panel; NaN for a q outside [x[0], x[-1]] or NaN). x, f, cum (n_nodes,) and q (any shape) are
-        contiguous float64 CUDA tensors on the context's device (anything else raises ValueError); returns a
-        tensor of q's shape. Waits for torch's current stream before the call and for the result after it."""
+    def _mesh_queries(self, call, x, f, cum, q, what):
+        """aq_mesh_eval / aq_mesh_invert on checked tensors: one output per element of q, in q's shape."""
         import torch
         dev = torch.device("cuda", self.device)
 
@@ -559,13 +556,35 @@ class Context:
         want(x, "x")
         want(f, "f", (n,))
         want(cum, "cum", (n,))
-        want(q, "q")
+        want(q, what)
         out = torch.empty_like(q)
         torch.cuda.current_stream(dev).synchronize()
-        _check(self.L.aq_mesh_eval(self._h, n, x.data_ptr(), f.data_ptr(), cum.data_ptr(), q.numel(), q.data_ptr(),
-                                   out.data_ptr()), "aq_mesh_eval")
+        _check(getattr(self.L, call)(self._h, n, x.data_ptr(), f.data_ptr(), cum.data_ptr(), q.numel(), q.data_ptr(),
+                                     out.data_ptr()), call)
         self.synchronize()
         return out
+
+    def mesh_eval(self, x, f, cum, q):
+        """The integral from x[0] to every q on a mesh of integrate_mesh (aq_mesh_eval: the trapezoid rule on the
+        partial panel; NaN for a q outside [x[0], x[-1]] or NaN). x, f, cum (n_nodes,) and q (any shape) are
+        contiguous float64 CUDA tensors on the context's device (anything else raises ValueError); returns a
+        tensor of q's shape. Waits for torch's current stream before the call and for the result after it."""
+        return self._mesh_queries("aq_mesh_eval", x, f, cum, q, "q")
+
+    def mesh_invert(self, x, f, cum, y):
+        """The x at which the integral from x[0] reaches every y, on a mesh of integrate_mesh whose cum is
+        non-decreasing (aq_mesh_invert: the root of mesh_eval's trapezoid on the panel cum[k] <= y <= cum[k+1]; NaN
+        for a y outside [cum[0], cum[-1]] or NaN). The tensors, the ValueErrors and the waiting are mesh_eval's;
+        returns a tensor of y's shape."""
+        return self._mesh_queries("aq_mesh_invert", x, f, cum, y, "y")
+
+    def mesh_sample(self, x, f, cum, n, generator=None):
+        """n samples of the density F / integral(F) on a mesh with F >= 0, by inverse-CDF sampling:
+        mesh_invert(x, f, cum, u * cum[-1]) for u = torch.rand(n) in float64 on the mesh's device; reproducible for
+        a seeded torch.Generator of that device."""
+        import torch
+        u = torch.rand(int(n), dtype=torch.float64, device=cum.device, generator=generator)
+        return self.mesh_invert(x, f, cum, u * cum[-1])
 
 
     # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------

@@ -2310,6 +2310,46 @@ int aq_mesh_eval(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const double*
     return AQ_OK;
 }
 
+// aq_mesh_invert's two instances of k_mesh_invert (aquad.hip) and the switch between them; the constants are the
+// measured ones of DESIGN.md "Mesh inversion" (profiles/mesh_invert/).
+constexpr int MINV_LOG_TAB = 11;               // the staged instance's table: 2048 entries of cum, 16 KiB of LDS
+constexpr int MINV_WG_PER_CU = 8;              // its grid: workgroups per CU (every wave slot; 8 x 16 KiB of the CU's 160)
+constexpr size_t MINV_QPT = 4;                 // ... and no more workgroups than give every thread this many queries
+constexpr size_t MINV_STAGED_MIN_NQ = 1 << 21; // fewer queries than this: the plain search (the staging does not pay)
+
+int aq_mesh_invert(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const double* d_f, const double* d_cum, size_t nq,
+                   const double* d_y, double* d_out) {
+    if (!ctx || n_nodes < 3) return AQ_EINVAL;
+    if (nq > 0 && (!d_x || !d_f || !d_cum || !d_y || !d_out)) return AQ_EINVAL;
+    if (nq == 0) return AQ_OK;
+    if ((nq + 255) / 256 > 0x7fffffffull) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    // AQ_MESH_INVERT=0 / 1 in the environment, read per call, forces the plain / the staged instance
+    const int force = env_int("AQ_MESH_INVERT", -1);
+    const bool staged = force == 0 ? false : force == 1 ? true : nq >= MINV_STAGED_MIN_NQ;
+    const uint64_t last = n_nodes - 2;   // m - 1, the last index the search may return
+    auto kernel = k_mesh_invert<0>;
+    unsigned grid = (unsigned)((nq + 255) / 256), sh = 0, entries = 0, top = 0;
+    if (staged) {
+        kernel = k_mesh_invert<MINV_LOG_TAB>;
+        while ((last >> sh) + 1 > (1ull << MINV_LOG_TAB)) ++sh;
+        entries = (unsigned)((last >> sh) + 1);
+        // the first halving step: 2 * top is the least power of two >= entries (one entry: no step)
+        if (entries > 1) for (top = 1; 2 * top < entries; top *= 2) {}
+        const size_t want = (nq + 256 * MINV_QPT - 1) / (256 * MINV_QPT);
+        grid = (unsigned)std::min<size_t>(want, (size_t)std::max(ctx->num_cus, 1) * MINV_WG_PER_CU);
+    } else {
+        while (sh < 64 && (last >> sh) != 0) ++sh;   // 2^sh > m - 1: the halving steps reach every index
+    }
+    EventPair ev;   // (aq_kernel_timing: tools/try_mesh_invert.py times the two instances with it)
+    int rc = timing_begin(ctx, ev);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (unsigned long long)n_nodes, d_x, d_f, d_cum, nq,
+                       d_y, d_out, sh, entries, top);
+    AQ_HIP(hipGetLastError());
+    return timing_end(ctx, ev);
+}
+
 int aq_kernel_timing(aq_ctx* ctx, int enable) {
     if (!ctx) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));

@@ -907,6 +907,84 @@ __global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, c
     out[i] = cum[lo] + (fk + fq) * h / 2;
 }
 
+// The x at which the running integral reaches y (aq_mesh_invert): k = the largest index <= m - 1 with cum_k <= y,
+// then the stable root of r = f_k h + s h^2 / 2 on that panel, one IEEE operation per step (the header states
+// them). The search is the cost -- 21 halving steps on the 1.5 M nodes of eps = 1e-10, each a dependent load -- and
+// every step tests the one monotone predicate "index <= m - 1 and cum <= y" at lo + 2^b, b counting down, so for a
+// non-decreasing cum any split of the steps returns the k defined above, equal runs included. Two instances:
+//   LOG_TAB == 0  every step in global memory, one query per lane: sh = the bits of m - 1 (few queries);
+//   LOG_TAB  > 0  every workgroup stages cum[j << sh], j < entries <= 2^LOG_TAB, into LDS (sh the least stride that
+//                 fits; pad = NaN, which no y is >=, so the pad is never stepped onto), answers its queries
+//                 grid-stride, and takes the steps above bit sh in the table -- halving from `top`, 2 * top the
+//                 least power of two >= entries -- and only the sh below it in global memory. sh == 0
+//                 (m <= 2^LOG_TAB): the table is cum.
+// Either way the last three steps run on registers: the 8 nodes from lo and the one after them, loaded in one round
+// trip, are also the panel's cum_k and cum_k+1. For any cum, monotone or not, a table index stays below `entries`
+// and a node index in [0, m - 1] (loads past it are clamped to m and not looked at).
+template <int LOG_TAB>
+__global__ __launch_bounds__(256) void k_mesh_invert(unsigned long long n_nodes, const double* __restrict__ x,
+                                                     const double* __restrict__ f, const double* __restrict__ cum,
+                                                     size_t nq, const double* __restrict__ y, double* __restrict__ out,
+                                                     unsigned sh, unsigned entries, unsigned top) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const unsigned long long last = n_nodes - 2;   // m - 1: the largest k
+    __shared__ double tab[1u << LOG_TAB];
+    if constexpr (LOG_TAB > 0) {
+        const unsigned fill = top ? 2 * top : 1;   // the steps read tab[1 .. 2 * top - 1]
+        for (unsigned j = threadIdx.x; j < fill; j += 256) tab[j] = j < entries ? cum[(unsigned long long)j << sh] : nan;
+        __syncthreads();
+    }
+    const double c0 = cum[0], cm = cum[last + 1];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (size_t)gridDim.x * 256) {
+        const double q = y[i];
+        if (!(q >= c0 && q <= cm)) {   // outside, or NaN
+            out[i] = nan;
+            continue;
+        }
+        unsigned long long lo = 0;
+        if constexpr (LOG_TAB > 0) {
+            unsigned j = 0;
+            for (unsigned step = top; step; step >>= 1)
+                if (tab[j + step] <= q) j += step;
+            lo = (unsigned long long)j << sh;
+        }
+        for (unsigned b = sh; b-- > 3;) {
+            const unsigned long long mid = lo + (1ull << b);
+            const double c = cum[min(mid, last)];
+            if (mid <= last && c <= q) lo = mid;
+        }
+        // steps 4, 2, 1 on v[e] = cum[lo + e], e <= rem in range. (Where fewer than three steps were left, sh < 3,
+        // the run of 8 is wider than needed and holds the answer all the same: lo <= k.)
+        const unsigned long long rem = last - lo;
+        double v[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) v[e] = cum[min(lo + e, last + 1)];
+        const bool t4 = 4 <= rem && v[4] <= q;
+        const unsigned e2 = t4 ? 6 : 2;                 // the candidates at lo + e2 - 1 .. lo + e2 + 2
+        const double a1 = t4 ? v[5] : v[1], a2 = t4 ? v[6] : v[2], a3 = t4 ? v[7] : v[3], a4 = t4 ? v[8] : v[4];
+        const bool t2 = e2 <= rem && a2 <= q;
+        const unsigned e1 = e2 + (t2 ? 1 : -1);         // ... at lo + e1, lo + e1 + 1
+        const double c1 = t2 ? a3 : a1, c2 = t2 ? a4 : a2;
+        const bool t1 = e1 <= rem && c1 <= q;
+        const unsigned long long k = lo + e1 - (t1 ? 0 : 1);
+        const double ck = t1 ? c1 : t2 ? a2 : t4 ? v[4] : v[0];
+        const double ck1 = t1 ? c2 : c1;
+        double res = nan;
+        if (ck <= q && q <= ck1) {   // (fails only where cum is not non-decreasing)
+            const double xk = x[k], fk = f[k];
+            const double w = x[k + 1] - xk;
+            const double r = q - ck;
+            const double s = (f[k + 1] - fk) / w;
+            const double disc = fmax(fk * fk + (2 * s) * r, 0.0);
+            const double den = fk + __dsqrt_rn(disc);
+            double h = r == 0 ? 0.0 : (2 * r) / den;
+            h = fmin(h, w);
+            res = xk + h;
+        }
+        out[i] = res;
+    }
+}
+
 // Gather n slots' totals into a caller device buffer as f64 [area, tasks, accepted, error] rows,
 // ready for one collective (counts are exact in f64 below 2^53). One thread per slot: the area is
 // the correctly rounded value of the slot's exact accumulator.
