@@ -203,7 +203,13 @@ int aq_integrate_levels(aq_ctx *ctx, const aq_problem *p, aq_result *res, uint64
  * the device counter *d_n_out, which the call zeroes first), accepted ones add into the device
  * accumulator d_acc[8] = {area hi, area lo (double-double), tasks, accepted, error bits, deepest
  * level, 0, 0}; the caller zeroes d_acc once per integral. Both calls are asynchronous on the
- * context's stream and never read device memory from the host. */
+ * context's stream and never read device memory from the host.
+ * The area is exact to the double-double's own rounding: with n accepted records of areas t_i (each the
+ * reference's double larea + rarea), |d_acc[0] + d_acc[1] - sum t_i| <= n * 2^-100 * sum |t_i|, whatever the
+ * order the lanes, blocks and folds add them in (the bound of aq_integrate_mesh's cum; aq_level_narrow too).
+ * A step runs min(ceil(n_in / 1024), 8192) workgroups, each striding over the level in chunks of 1024 records;
+ * AQ_LEVEL_GRID=<n> in the environment (read at aq_ctx_create, clamped to 1..8192) puts n in place of the 8192,
+ * so that a small level runs several chunks per workgroup -- for tests; the results do not depend on it. */
 int aq_frontier_root(aq_ctx *ctx, int integrand, double a, double b, double *d_out);
 int aq_level_step(aq_ctx *ctx, int integrand, const double *d_in, uint32_t n_in, double *d_out, uint32_t cap_out,
                   double eps, int depth, int max_depth, uint32_t *d_n_out, double *d_acc);

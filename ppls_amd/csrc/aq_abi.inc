@@ -277,6 +277,7 @@ struct aq_ctx {
     PinBuf<double> h_facc;             // pinned copy
     DevBuf<LevelPart> d_lparts{&dev_bytes};   // frontier engine: per-block partials of one level step
     bool defer_fold = false;           // aq_level_defer_fold: level steps leave their rows for one later fold
+    int level_grid = 0;                // aq_level_step's grid cap (MAXB, or AQ_LEVEL_GRID), set at create
     int lp_pending = 0;                // level-step rows written and not yet folded
     double* lp_acc = nullptr;          // ... into this accumulator (the caller's)
     // the accepted mesh (aq_integrate_mesh), allocated by its first call and grown on demand
@@ -841,6 +842,9 @@ int aq_device_count(int* count) {
     return n > 0 ? AQ_OK : AQ_ENODEV;
 }
 
+constexpr int MAXB = 8192;            // level-step grid cap (grid-stride beyond); AQ_LEVEL_GRID sets a smaller one
+constexpr int LP_CAP = 8 * MAXB;      // level-step rows held for one deferred fold
+
 static int ctx_init(aq_ctx* c, int device) {
     c->device = device;
     AQ_HIP(hipSetDevice(device));
@@ -863,6 +867,8 @@ static int ctx_init(aq_ctx* c, int device) {
         const double v = atof(e);
         if (v > 0) c->stall_ms = v;
     }
+    c->level_grid = MAXB;
+    if (const char* e = getenv("AQ_LEVEL_GRID")) c->level_grid = std::min(std::max(atoi(e), 1), MAXB);
     AQ_HIP(c->stream.create());
     const size_t G = (size_t)c->grid;
     AQ_HIP(c->d_tab.alloc(128, false));
@@ -2056,9 +2062,6 @@ int aq_frontier_root(aq_ctx* ctx, int integrand, double a, double b, double* d_o
     return AQ_OK;
 }
 
-constexpr int MAXB = 8192;            // level-step grid cap (grid-stride beyond)
-constexpr int LP_CAP = 8 * MAXB;      // level-step rows held for one deferred fold
-
 // Fold the level-step rows written since the last fold into their accumulator (one k_level_fold).
 static int fold_pending(aq_ctx* ctx) {
     if (ctx->lp_pending > 0) {
@@ -2080,7 +2083,8 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
     AQ_HIP(ctx->d_lparts.grow(LP_CAP));
     if (!d_n_in) AQ_HIP(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), ctx->stream));
     if (n_in == 0) return AQ_OK;
-    const int grid = (int)std::min<size_t>(((size_t)n_in + LEVEL_T * LEVEL_R - 1) / (LEVEL_T * LEVEL_R), (size_t)MAXB);
+    const int grid = (int)std::min<size_t>(((size_t)n_in + LEVEL_T * LEVEL_R - 1) / (LEVEL_T * LEVEL_R),
+                                           (size_t)ctx->level_grid);
     // this step's rows follow the pending ones (folded first if they belong elsewhere or would not fit)
     if (ctx->lp_pending && (d_acc != ctx->lp_acc || ctx->lp_pending + grid > LP_CAP) && (rc = fold_pending(ctx)))
         return rc;

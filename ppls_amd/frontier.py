@@ -115,7 +115,8 @@ class HipStepper:
         per = [int(v) for v in t[:int(r.levels)]]
         return FrontierResult(area=r.area, tasks=int(r.tasks), accepted=int(r.accepted), levels=int(r.levels),
                               tasks_per_rank=[int(r.tasks)], accepted_per_rank=[int(r.accepted)], tasks_per_level=per,
-                              rebalances=0, moved_records=0, max_frontier=max(per) if per else 0)
+                              rebalances=0, moved_records=0, max_frontier=max(per) if per else 0,
+                              leaves_per_level=[int(v) for v in lv[:int(r.levels)]])
 
     def defer_folds(self, enable: bool):
         """Level steps leave their partial rows for one fold at the next sync (aq_level_defer_fold)."""
@@ -137,6 +138,7 @@ class FrontierResult:
     rebalances: int = 0
     moved_records: int = 0
     max_frontier: int = 0
+    leaves_per_level: List[int] = field(default_factory=list)   # (aq_frontier_integrate's; the Python loop leaves it empty)
 
 
 CHAIN_LEVELS = 4   # one GPU: levels chained on the device between host looks at the frontier size

@@ -20,6 +20,8 @@ Outputs (data only, no code of the reference):
   sin_bits.npz    x, F(x) = sin(1.0/x) (config 4's F macro, host libm) as uint64 bit patterns
   edges.json      trees at the edges of the documented domain (|x| = 170, subnormal areas, eps = 0, 2^-900, 2^900),
                   on which the restated and the host-libm oracle modes must agree
+  recip_hard_bits.npz  x, cosh(x) (host libm) where 0.5 / exp(x) lies within 100 * 2^-106 (relative) of a rounding
+                  midpoint (needs sympy)
 """
 import json
 import os
@@ -139,6 +141,44 @@ def libm_bits():
     assert (O.cosh(x).view(np.uint64) == cosh.view(np.uint64)).all()
     assert (O.exp(expx).view(np.uint64) == exp.view(np.uint64)).all()
     print("libm_bits:", x.size, "points;", tp.size, "distinct-ish tree points at 1e-10")
+
+
+def recip_hard(max_delta=100):
+    """cosh's hard reciprocals. For 0.5 ln 2 <= |x| < 22 glibc's cosh is 0.5 t + 0.5 / t with t = exp(|x|). Take a
+    53-bit T with T N = 2^106 - delta for an odd N and a small delta > 0: 2^105 / T = N / 2 + delta / (2 T), so 0.5 / t
+    for t = T 2^a lies delta 2^-106 (relative) above the midpoint of two doubles -- a division that is not correct to
+    about 100 bits before its last rounding gets it wrong. The T come from the divisors of 2^106 - delta (sympy), the x
+    from the neighbours of log(t) whose host-libm exp is t exactly, t in [1.4143, 8) (further up 0.5 / t no longer
+    moves cosh's last bit). Output: recip_hard_bits.npz (x, host-libm cosh(x), delta)."""
+    import math
+
+    from sympy import factorint
+    xs, ds = [], []
+    for delta in range(1, max_delta + 1):
+        n = (1 << 106) - delta
+        div = [1]
+        for p, k in factorint(n).items():
+            div = [d * p ** i for d in div for i in range(k + 1)]
+        for T in sorted(div):
+            if not ((1 << 52) <= T < (1 << 53) and (n // T) & 1):
+                continue
+            for a in (-52, -51, -50):
+                t = math.ldexp(float(T), a)
+                if not 1.4143 <= t < 8.0:
+                    continue
+                cand = [math.log(t)]
+                for _ in range(8):
+                    cand = [math.nextafter(cand[0], -math.inf)] + cand + [math.nextafter(cand[-1], math.inf)]
+                cand = np.array(cand)
+                for x in cand[O.exp(cand, O.HOST_LIBM) == t][:2]:
+                    xs.append(float(x))
+                    ds.append(delta)
+    x = np.array(xs)
+    cosh = O.cosh(x, O.HOST_LIBM)
+    assert (O.cosh(x).view(np.uint64) == cosh.view(np.uint64)).all()   # the restatement must already agree
+    np.savez_compressed(os.path.join(OUT, "recip_hard_bits.npz"), x=x.view(np.uint64), cosh=cosh.view(np.uint64),
+                        delta=np.array(ds, np.int64))
+    print("recip_hard:", x.size, "points from", len(set(ds)), "values of delta")
 
 
 def _batch10_part(rng):
@@ -321,7 +361,7 @@ if __name__ == "__main__":
     if not shutil.which(MPIRUN) and not os.path.exists(MPIRUN):
         print("warning: no mpirun; reference stdout will not be recorded")
     O.build()
-    which = sys.argv[1:] or ["trees", "plugin", "libm_bits", "sin_bits", "batch", "deep", "edges"]
+    which = sys.argv[1:] or ["trees", "plugin", "libm_bits", "sin_bits", "batch", "deep", "edges", "recip_hard"]
     for name in which:
         {"trees": trees, "plugin": plugin, "libm_bits": libm_bits, "sin_bits": sin_bits, "batch": batch,
-         "deep": deep, "edges": edges}[name]()
+         "deep": deep, "edges": edges, "recip_hard": recip_hard}[name]()
