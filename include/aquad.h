@@ -476,8 +476,9 @@ int aq_device_batch_check(aq_ctx *ctx, uint64_t *invalid_rows);
  * table in LDS; both return the same k, and AQ_MESH_INVERT=0 / 1 in the environment, read per call, forces the
  * first / the second.
  * Not covered: meshes from the persistent kernel (aq_integrate*, shards, aq_group, the batches, the
- * tolerance-driven batch), AQ_F_PARAM, several meshes per call (aq_mesh_eval and aq_mesh_invert alike), inversion
- * of non-monotone meshes, host-memory outputs (callers copy), the CLI. */
+ * tolerance-driven batch), inversion of non-monotone meshes, host-memory outputs (callers copy), the CLI.
+ * AQ_F_PARAM and several meshes per call are aq_integrate_mesh_batch's, with aq_mesh_eval_batch and
+ * aq_mesh_invert_batch (below). */
 typedef struct {
     double  *x;      /* DEVICE [cap_nodes]: x_0 = a < x_1 < ... < x_m = b, m = 2 * accepted */
     double  *f;      /* DEVICE [cap_nodes]: F(x_k), the values the tree evaluated */
@@ -490,6 +491,72 @@ int aq_mesh_eval(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const double 
                  size_t nq, const double *d_q, double *d_out);
 int aq_mesh_invert(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const double *d_f, const double *d_cum,
                    size_t nq, const double *d_y, double *d_out);
+
+/* ---- batched meshes: many integrals' leaves, cum and queries in one call ---------------------------
+ * aq_integrate_mesh_batch builds the meshes of n integrals of one integrand -- AQ_F_PARAM included, row i under
+ * theta[i * aq_param_count() ..] -- in ONE level-synchronous run: the records of every row's depth d share one
+ * frontier, so a level is one launch whatever n. Every pointer of aq_mesh_batch_io is DEVICE memory of the
+ * context's device. The call blocks, as aq_integrate_mesh does; the inputs must be complete when it is made.
+ * Per-row mesh. Row i with a valid domain gets exactly the mesh aq_integrate_mesh defines for [a[i], b[i]] at eps:
+ * 2 * accepted_i + 1 nodes at x / f / cum [offsets[i], offsets[i+1]), x, f and level the values the task steps
+ * computed, cum restarting at 0 with the row; tasks_i = 2 * accepted_i - 1. level[k] is the depth of the task that
+ * owns panel k -> k+1; at a row's last node it is unspecified.
+ * Invalid rows. The domain rule of AQ_EINVAL above, checked on the device by the predicate the host calls use (as
+ * aq_integrate_batch_device does). A row that fails gets AQ_ROW_INVALID in status, no nodes (offsets[i+1] ==
+ * offsets[i]), area NaN, accepted = tasks = 0 and no record in the frontier; it disturbs no other row.
+ * Running integral. Each row's prefix is carried in double-double and adds that row's terms alone (a segmented
+ * scan: no global prefix, nothing subtracted), so it errs by at most accepted_i * 2^-100 * Σ|terms of row i| and
+ * every cum value is the correctly rounded exact prefix of its own row or that value's neighbour, whatever the
+ * magnitudes of the rows before it. area[i] is the row's last cum.
+ * Determinism. For given inputs every output is bit-identical from run to run and for every sync_every (the
+ * leaves are sorted by (row, l), unique; the scan's tree depends on the rows' leaf counts alone).
+ * Capacity. info->n_nodes = 2 * leaves + valid rows, written even when it exceeds cap_nodes: the trees are then
+ * still walked to their end -- leaves past the capacity are counted, not stored -- the return is AQ_EOVERFLOW,
+ * offsets, the node arrays and the per-row outputs but status are unspecified and nothing is written at or past
+ * cap_nodes: retry with the size reported.
+ * Frontier overflow. A level of all rows together that exceeds frontier_cap records: AQ_EOVERFLOW with
+ * info->n_nodes = 0. info->widest_level of a successful run, the largest level, is the frontier_cap that suffices.
+ * AQ_EDEPTH when any row refines at max_depth: info->n_nodes = 0, the node arrays are unspecified, and status
+ * carries AQ_ROW_DEPTH on exactly the rows whose unbounded tree has more than max_depth levels. status (the
+ * AQ_ROW_INVALID and AQ_ROW_DEPTH bits) is written whatever the return, once the arguments were accepted.
+ * AQ_EINVAL: a NULL ctx, io, a, b, offsets, x, f, cum or info; a theta that does not go with the integrand (the
+ * rule of the _err calls); a bad eps, max_depth or sync_every; frontier_cap < max(n, 2); cap_nodes < 3 or > 2^31.
+ * n == 0: AQ_OK, info zeroed, nothing enqueued. info->invalid_rows, leaves, tasks and levels describe the run.
+ * Device memory. The batch frontier (32 + 4 bytes a record of frontier_cap, twice; the records are the frontier
+ * engine's buffers), leaf records (48 bytes per leaf of cap_nodes / 2; aq_integrate_mesh's), sort arrays and
+ * scratch, row tables and scan partials are context-owned, allocated by the first such call, grown on demand and
+ * freed with the context; aq_ctx_device_bytes does not move before that call, nor at a second call of the same
+ * sizes.
+ * aq_mesh_eval_batch / aq_mesh_invert_batch answer nq_per_row queries for each of the n rows of such a mesh: row
+ * i's query j, d_q[i * nq_per_row + j], is bit for bit what aq_mesh_eval / aq_mesh_invert (its plain search) return
+ * for it on the slice [offsets[i], offsets[i+1]) -- the NaN cases included -- and a row of fewer than 3 nodes
+ * answers NaN. One query per lane, a binary search inside the row's slice. The calls only enqueue on the
+ * context's stream, own no device memory and read nothing on the host (aq_synchronize orders the output).
+ * AQ_EINVAL: a NULL ctx, or a NULL array with n * nq_per_row > 0.
+ * Not covered: shards and aq_group, meshes from the persistent kernel, the CLI, a device-side retry when a
+ * capacity is missed, a per-row eps, a staged-table search for very many queries per row. */
+typedef struct {
+    const double *a, *b;        /* DEVICE [n] */
+    const double *theta;        /* DEVICE [n * aq_param_count()] row-major; non-NULL exactly for AQ_F_PARAM */
+    uint64_t *offsets;          /* DEVICE [n + 1]: row i's nodes are [offsets[i], offsets[i+1]) of x / f / cum */
+    double   *x, *f, *cum;      /* DEVICE [cap_nodes] */
+    uint8_t  *level;            /* DEVICE [cap_nodes] or NULL */
+    double   *area;             /* DEVICE [n] or NULL: the row's last cum (NaN for an invalid row) */
+    uint64_t *accepted, *tasks; /* DEVICE [n] or NULL */
+    uint32_t *status;           /* DEVICE [n] or NULL: 0, or AQ_ROW_* bits */
+    int32_t   max_depth;        /* as aq_problem.max_depth */
+    int32_t   reserved;
+} aq_mesh_batch_io;
+typedef struct {
+    uint64_t n_nodes, leaves, tasks, invalid_rows;
+    uint32_t levels, widest_level;
+} aq_mesh_batch_info;
+int aq_integrate_mesh_batch(aq_ctx *ctx, size_t n, const aq_mesh_batch_io *io, double eps, int integrand,
+                            uint32_t frontier_cap, int sync_every, uint64_t cap_nodes, aq_mesh_batch_info *info);
+int aq_mesh_eval_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                       const double *d_cum, size_t nq_per_row, const double *d_q, double *d_out);
+int aq_mesh_invert_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                         const double *d_cum, size_t nq_per_row, const double *d_y, double *d_out);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel, and of aq_mesh_invert's kernel, on

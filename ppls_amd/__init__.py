@@ -14,6 +14,7 @@ from .aquad import (  # noqa: F401
     Context,
     DeviceBatch,
     Group,
+    MeshBatch,
     Problem,
     Result,
     TolResult,
@@ -26,6 +27,6 @@ from .aquad import (  # noqa: F401
     user_integrand_name,
 )
 
-__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "DeviceBatch", "Group", "Problem", "Result", "TolResult",
+__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "DeviceBatch", "Group", "MeshBatch", "Problem", "Result", "TolResult",
            "exact_round",
            "farmer", "format_reference", "integrate", "param_count", "param_integrand_name", "user_integrand_name"]

@@ -26,6 +26,7 @@ EXPORTS = (
     "aq_integrate_batch_tol",
     "aq_integrate_batch_device", "aq_device_batch_check",
     "aq_integrate_mesh", "aq_mesh_eval", "aq_mesh_invert",
+    "aq_integrate_mesh_batch", "aq_mesh_eval_batch", "aq_mesh_invert_batch",
 )
 
 AQ_MAX_LEVELS = 128
@@ -69,6 +70,19 @@ class aq_device_io(ctypes.Structure):
 class aq_mesh_io(ctypes.Structure):
     """Device pointers (aquad.h aq_mesh_io): the mesh's x, f, cum [cap_nodes] and level [cap_nodes - 1] (or NULL)."""
     _fields_ = [(name, ctypes.c_void_p) for name in ("x", "f", "cum", "level")]
+
+
+class aq_mesh_batch_io(ctypes.Structure):
+    """Device pointers (aquad.h aq_mesh_batch_io): a, b, theta in; offsets [n + 1], x, f, cum, level [cap_nodes] and
+    the per-row area, accepted, tasks, status [n] out."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("a", "b", "theta", "offsets", "x", "f", "cum", "level", "area",
+                                                     "accepted", "tasks", "status")] + \
+               [("max_depth", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class aq_mesh_batch_info(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
+                ("invalid_rows", ctypes.c_uint64), ("levels", ctypes.c_uint32), ("widest_level", ctypes.c_uint32)]
 
 
 _lib = None
@@ -162,6 +176,10 @@ def load(build_if_missing=True):
         "aq_integrate_mesh": ([vp, P, ctypes.c_uint32, c_int, ctypes.c_uint64, ctypes.POINTER(aq_mesh_io), R, up], c_int),
         "aq_mesh_eval": ([vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
         "aq_mesh_invert": ([vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
+        "aq_integrate_mesh_batch": ([vp, ctypes.c_size_t, ctypes.POINTER(aq_mesh_batch_io), c_dbl, c_int, ctypes.c_uint32,
+                                     c_int, ctypes.c_uint64, ctypes.POINTER(aq_mesh_batch_info)], c_int),
+        "aq_mesh_eval_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
+        "aq_mesh_invert_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

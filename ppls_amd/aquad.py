@@ -89,6 +89,24 @@ DeviceBatch = collections.namedtuple("DeviceBatch", "area tasks accepted err_abs
 ROW_TIMEOUT, ROW_OVERFLOW, ROW_DEPTH, ROW_INVALID = 1, 2, 4, 8   # aquad.h AQ_ROW_*
 
 
+class MeshBatch:
+    """Context.integrate_mesh_batch's result, all torch CUDA tensors: offsets (n + 1, int64) with row i's nodes at
+    [offsets[i], offsets[i+1]) of x, f, cum (float64) and level (uint8), all trimmed to n_nodes; per row area
+    (float64: the row's last cum, NaN for an invalid row), accepted, tasks (int64) and status (int32: 0 or ROW_*
+    bits); and the run's n_nodes, leaves, total_tasks, invalid_rows, levels, widest_level."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return self.offsets.shape[0] - 1
+
+    def row(self, i):
+        """Views of row i's (x, f, cum, level): 2 * accepted[i] + 1 nodes (level: one fewer), none for an invalid row."""
+        o0, o1 = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.x[o0:o1], self.f[o0:o1], self.cum[o0:o1], self.level[o0:max(o1 - 1, o0)]
+
+
 def _check(rc, what):
     if rc != 0:
         msg = _lib.load().aq_strerror(rc).decode()
@@ -585,6 +603,113 @@ class Context:
         import torch
         u = torch.rand(int(n), dtype=torch.float64, device=cum.device, generator=generator)
         return self.mesh_invert(x, f, cum, u * cum[-1])
+
+    # -- batched meshes: many integrals' leaves, cum and quantiles in one call ----------------
+    def integrate_mesh_batch(self, a, b, eps, integrand=COSH4, theta=None, cap_nodes=None, frontier_cap=1 << 22,
+                             sync_every=4, max_depth=0) -> MeshBatch:
+        """The adaptive meshes of n integrals [a[i], b[i]] of one integrand in one level-synchronous run
+        (aq_integrate_mesh_batch) -- PARAM included, row i under theta[i]. a, b (n,) and theta (n, param_count()) are
+        contiguous float64 CUDA tensors on the context's device (anything else raises ValueError). Returns a MeshBatch.
+        A row outside the domain gets status ROW_INVALID, no nodes and a NaN area instead of failing the call. Blocks.
+        cap_nodes=None sizes the arrays from a first integrate_batch_device call: 2 * sum(accepted) + n. A cap_nodes
+        that is too small raises AquadError (code AQ_EOVERFLOW) whose n_nodes attribute is the size to retry with."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def want(t, shape, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float64 and
+                    tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of shape {shape} on {dev}")
+            return t
+
+        if not isinstance(a, torch.Tensor) or a.dim() != 1:
+            raise ValueError("a must be a 1-d torch tensor")
+        n = a.shape[0]
+        want(a, (n,), "a")
+        want(b, (n,), "b")
+        if (integrand == PARAM) != (theta is not None):
+            raise ValueError("theta goes with the PARAM integrand, and with it only")
+        if theta is not None:
+            want(theta, (n, param_count()), "theta")
+        if cap_nodes is None:
+            first = self.integrate_batch_device(a, b, eps, integrand=integrand, theta=theta, max_depth=max_depth)
+            cap_nodes = max(2 * int(first.accepted.sum()) + n, 3)
+        cap_nodes = int(cap_nodes)
+        if cap_nodes < 3:
+            raise ValueError("cap_nodes must be at least 3")
+        x, f, cum = (torch.empty(cap_nodes, dtype=torch.float64, device=dev) for _ in range(3))
+        level = torch.empty(cap_nodes, dtype=torch.uint8, device=dev)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        area = torch.empty(n, dtype=torch.float64, device=dev)
+        accepted, tasks = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2))
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # the inputs are complete, the allocator's blocks free
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        io = _lib.aq_mesh_batch_io(ptr(a), ptr(b), ptr(theta), ptr(offsets), ptr(x), ptr(f), ptr(cum), ptr(level),
+                                   ptr(area), ptr(accepted), ptr(tasks), ptr(status), int(max_depth), 0)
+        info = _lib.aq_mesh_batch_info()
+        rc = self.L.aq_integrate_mesh_batch(self._h, n, ctypes.byref(io), float(eps), integrand, int(frontier_cap),
+                                            int(sync_every), cap_nodes, ctypes.byref(info))
+        if rc == -4 and info.n_nodes:   # AQ_EOVERFLOW of cap_nodes (the frontier's leaves n_nodes at 0)
+            e = AquadError(f"aq_integrate_mesh_batch: the meshes have {info.n_nodes} nodes, cap_nodes is {cap_nodes} "
+                           f"(code {rc})", rc)
+            e.n_nodes = int(info.n_nodes)
+            raise e
+        _check(rc, "aq_integrate_mesh_batch")
+        m = int(info.n_nodes)
+        return MeshBatch(offsets=offsets, x=x[:m], f=f[:m], cum=cum[:m], level=level[:m], area=area, accepted=accepted,
+                         tasks=tasks, status=status, n_nodes=m, leaves=int(info.leaves), total_tasks=int(info.tasks),
+                         invalid_rows=int(info.invalid_rows), levels=int(info.levels),
+                         widest_level=int(info.widest_level))
+
+    def _mesh_batch_queries(self, call, mesh, q, what):
+        """aq_mesh_eval_batch / aq_mesh_invert_batch on checked tensors (_mesh_queries's checks and waiting): q is
+        (n, nq), one row of queries per row of the mesh; the output has q's shape."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def want(t, what, dtype=torch.float64, shape=None):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and
+                    t.is_contiguous() and (shape is None or tuple(t.shape) == shape)):
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor on {dev}" +
+                                 (f" of shape {shape}" if shape else ""))
+            return t
+
+        if not isinstance(mesh.x, torch.Tensor) or mesh.x.dim() != 1:
+            raise ValueError("mesh.x must be a 1-d torch tensor")
+        m, n = mesh.x.shape[0], len(mesh)
+        want(mesh.offsets, "mesh.offsets", torch.int64, (n + 1,))
+        want(mesh.x, "mesh.x")
+        want(mesh.f, "mesh.f", shape=(m,))
+        want(mesh.cum, "mesh.cum", shape=(m,))
+        want(q, what)
+        if q.dim() != 2 or q.shape[0] != n:
+            raise ValueError(f"{what} must have shape (n, nq) with n = {n} rows")
+        out = torch.empty_like(q)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(getattr(self.L, call)(self._h, n, mesh.offsets.data_ptr(), mesh.x.data_ptr(), mesh.f.data_ptr(),
+                                     mesh.cum.data_ptr(), q.shape[1], q.data_ptr(), out.data_ptr()), call)
+        self.synchronize()
+        return out
+
+    def mesh_eval_batch(self, mesh: MeshBatch, q):
+        """mesh_eval on every row of a MeshBatch: out[i, j] is the integral from row i's a to q[i, j] (NaN outside the
+        row's [a, b], for NaN, and on a row without nodes). q: (n, nq) contiguous float64 CUDA tensor."""
+        return self._mesh_batch_queries("aq_mesh_eval_batch", mesh, q, "q")
+
+    def mesh_invert_batch(self, mesh: MeshBatch, y):
+        """mesh_invert on every row of a MeshBatch: out[i, j] is the x at which row i's running integral reaches
+        y[i, j] (NaN outside [0, area[i]], for NaN, and on a row without nodes). y: (n, nq) as mesh_eval_batch's q."""
+        return self._mesh_batch_queries("aq_mesh_invert_batch", mesh, y, "y")
+
+    def mesh_quantiles(self, mesh: MeshBatch, u):
+        """The u-quantiles of every row's density F / integral(F): mesh_invert_batch(mesh, u * area[:, None]) for u of
+        shape (nq,) or (n, nq) in [0, 1]; returns (n, nq)."""
+        import torch
+        u = torch.as_tensor(u, dtype=torch.float64, device=mesh.area.device)
+        if u.dim() == 1:
+            u = u[None, :]
+        return self.mesh_invert_batch(mesh, (u * mesh.area[:, None]).contiguous())
 
 
     # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------

@@ -287,6 +287,16 @@ struct aq_ctx {
     DevBuf<unsigned> d_midx[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}}; // leaf indices in / out
     DevBuf<unsigned char> d_msort{&dev_bytes};      // the sort's scratch
     DevBuf<double2> d_mparts{&dev_bytes};           // the scan's block partials
+    // the batch of meshes (aq_integrate_mesh_batch), allocated by its first call and grown on demand; it runs in the
+    // frontier buffers and the single mesh's leaf, sort and partial arrays above, and adds:
+    DevBuf<unsigned> d_brow[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}};   // the frontier records' rows
+    DevBuf<unsigned> d_bkey[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}};   // the second sort's keys in / out
+    DevBuf<unsigned> d_bfirst{&dev_bytes};          // [n + 1] every row's first sorted leaf
+    DevBuf<unsigned> d_bnode{&dev_bytes};           // a sorted leaf's first node | its row's head bit
+    DevBuf<unsigned> d_bpflag{&dev_bytes};          // the segmented scan's "block has a head"
+    DevBuf<unsigned> d_bstatus{&dev_bytes};         // [n] the rows' status when the caller wants none
+    DevBuf<unsigned long long> d_binvalid{&dev_bytes};   // rows that failed the check (one word)
+    PinBuf<unsigned long long> h_bwords;            // pinned: the leaf count and the invalid rows
     HostBatch batch{&dev_bytes};       // the batch front end's rings and pinned copies (grown by its calls)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
     // rows on the device beside d_bounds, and their pinned staging ring
@@ -574,8 +584,8 @@ int ensure_err(aq_ctx* ctx) {
     return AQ_OK;
 }
 
-// with_fid for the stream launches: AQ_F_PARAM too (with_fid stays the three fixed integrands': no level or
-// frontier kernel is instantiated for id 3)
+// with_fid for the stream launches and the batch of meshes: AQ_F_PARAM too (with_fid stays the three fixed
+// integrands': the only level kernel instantiated for id 3 is the batch form, k_level_step<F_PARAM, BatchSink>)
 template <typename Fn>
 auto with_stream_fid(int integrand, Fn&& f) {
     if (integrand == AQ_F_PARAM) return f(std::integral_constant<int, F_PARAM>{});
@@ -2074,9 +2084,9 @@ static int fold_pending(aq_ctx* ctx) {
 
 static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint32_t n_in, const uint32_t* d_n_in,
                            double* d_out, uint32_t cap_out, double eps, int depth, int max_depth, uint32_t* d_n_out,
-                           double* d_acc, const LeafSink* sink = nullptr) {
+                           double* d_acc, const LeafSink* sink = nullptr, const BatchSink* bsink = nullptr) {
     if (!ctx || !d_n_out || !d_acc || (n_in && (!d_in || !d_out))) return AQ_EINVAL;
-    if (!integrand_ok(integrand)) return AQ_EINVAL;
+    if (!integrand_ok(integrand) && !(bsink && integrand == AQ_F_PARAM)) return AQ_EINVAL;
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
     int rc;
@@ -2089,7 +2099,13 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
     if (ctx->lp_pending && (d_acc != ctx->lp_acc || ctx->lp_pending + grid > LP_CAP) && (rc = fold_pending(ctx)))
         return rc;
     LevelPart* rows = ctx->d_lparts + ctx->lp_pending;
-    with_fid(integrand, [&](auto F) {
+    if (bsink)   // the batch form (aq_integrate_mesh_batch): every integrand, F_PARAM among them
+        with_stream_fid(integrand, [&](auto F) {
+            hipLaunchKernelGGL((k_level_step<decltype(F)::value, BatchSink>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
+                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
+                               ctx->d_tab, d_n_in, *bsink);
+        });
+    else with_fid(integrand, [&](auto F) {
         if (sink)   // the leaf-emitting form (aq_integrate_mesh)
             hipLaunchKernelGGL((k_level_step<decltype(F)::value, LeafSink>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
                                (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
@@ -2300,6 +2316,163 @@ int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, i
     return AQ_OK;
 }
 
+// Many meshes per call: frontier_run's loop over ONE frontier that holds every row's records of a depth (level 0:
+// the valid rows' roots, compacted by k_mesh_batch_roots; no narrow top -- level 0 is already n records wide, and a
+// small batch's few narrow levels cost a launch each as a lone mesh's levels past the top do), then the leaves
+// ordered by (row, l) and laid out row after row (aquad.hip k_mesh_batch_*). Blocks, as aq_integrate_mesh does.
+int aq_integrate_mesh_batch(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, double eps, int integrand,
+                            uint32_t frontier_cap, int sync_every, uint64_t cap_nodes, aq_mesh_batch_info* info) {
+    if (!ctx || !io || !info || !io->a || !io->b || !io->offsets || !io->x || !io->f || !io->cum) return AQ_EINVAL;
+    if (!theta_ok(integrand, io->theta)) return AQ_EINVAL;
+    if (!(eps >= 0.0) || io->max_depth < 0 || io->max_depth > AQ_MAX_LEVELS - 1 || sync_every < 1) return AQ_EINVAL;
+    if (frontier_cap < std::max<size_t>(n, 2)) return AQ_EINVAL;
+    if (cap_nodes < 3 || cap_nodes > (1ull << 31)) return AQ_EINVAL;
+    *info = aq_mesh_batch_info{};
+    if (n == 0) return AQ_OK;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const int max_depth = io->max_depth ? io->max_depth : AQ_DEFAULT_MAX_DEPTH;
+    const uint32_t cap = frontier_cap;
+    const unsigned nr = (unsigned)n;   // n <= frontier_cap < 2^32
+    const size_t cap_leaves = (size_t)(cap_nodes / 2);   // a mesh that fits has at most (cap_nodes - 1) / 2 leaves
+    int rc;
+    if ((rc = ensure_front(ctx, cap))) return rc;
+    for (int k = 0; k < 2; ++k) AQ_HIP(ctx->d_brow[k].grow(cap));
+    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
+    AQ_HIP(ctx->d_leafcnt.grow(1));
+    AQ_HIP(ctx->d_binvalid.grow(1));
+    AQ_HIP(ctx->d_bfirst.grow(n + 1));
+    if (!io->status) AQ_HIP(ctx->d_bstatus.grow(n));
+    AQ_HIP(ctx->d_facc.grow(8));
+    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
+    AQ_HIP(ctx->h_facc.grow(8));
+    AQ_HIP(ctx->h_bwords.grow(2));
+    unsigned* cnt = ctx->d_count;
+    double* acc = ctx->d_facc;
+    unsigned* status = io->status ? io->status : ctx->d_bstatus.get();
+    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
+    unsigned* row[2] = {ctx->d_brow[0].get(), ctx->d_brow[1].get()};
+    AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
+    AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
+    with_stream_fid(integrand, [&](auto F) {
+        hipLaunchKernelGGL((k_mesh_batch_roots<decltype(F)::value>), dim3((nr + 255u) / 256u), dim3(256), 0, ctx->stream,
+                           io->a, io->b, io->theta, nr, (Rec*)buf[0], row[0], cnt, status, ctx->d_binvalid.get(),
+                           ctx->d_tab);
+    });
+    AQ_HIP(hipGetLastError());
+    const bool defer0 = ctx->defer_fold;
+    ctx->defer_fold = true;
+    int depth = 0, since = 0;
+    unsigned long long bound = nr;   // level 0 holds at most n records; a level at most twice the one before
+    while (depth <= max_depth && depth < AQ_MAX_LEVELS) {
+        const BatchSink sink{LeafSink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves}, row[depth & 1],
+                             row[(depth + 1) & 1], io->theta, status, nr};
+        rc = level_step_impl(ctx, integrand, buf[depth & 1], (uint32_t)bound, cnt + depth, buf[(depth + 1) & 1], cap, eps,
+                             depth, max_depth, cnt + depth + 1, acc, nullptr, &sink);
+        if (rc) break;
+        ++depth;
+        bound = std::min<unsigned long long>(2 * bound, cap);
+        if (++since == sync_every) {
+            since = 0;
+            if ((rc = fold_pending(ctx))) break;
+            AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+            AQ_HIP(hipStreamSynchronize(ctx->stream));
+            const unsigned now = ctx->h_fcount[0];
+            if (now == 0) break;
+            if (now > cap) { rc = AQ_EOVERFLOW; break; }
+            bound = now;
+        }
+    }
+    ctx->defer_fold = defer0;
+    if (rc == AQ_OK) rc = fold_pending(ctx);
+    else (void)fold_pending(ctx);
+    AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_facc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_bwords, ctx->d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_bwords + 1, ctx->d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    info->invalid_rows = ctx->h_bwords[1];
+    if (rc) return rc;
+    const double* a = ctx->h_facc;
+    const unsigned* c = ctx->h_fcount;
+    if ((rc = err_from_bits((unsigned)a[4]))) return rc;   // a level past frontier_cap, or a refine at max_depth
+    if (c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
+    const uint64_t leaves = ctx->h_bwords[0];   // every accepted task emitted (or, past the capacity, counted) one leaf
+    info->leaves = leaves;
+    info->tasks = (uint64_t)a[2];
+    info->levels = (uint32_t)a[5];
+    for (int d = 0; d < AQ_MAX_LEVELS + 2; ++d) info->widest_level = std::max(info->widest_level, (uint32_t)c[d]);
+    info->n_nodes = 2 * leaves + (n - info->invalid_rows);
+    if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
+    const unsigned nl = (unsigned)leaves;
+    const unsigned grid = (nl + MESH_T - 1) / MESH_T, rgrid = (nr + 1 + MESH_T - 1) / MESH_T;
+    unsigned bits = 0;
+    while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;   // ceil(log2 n): the rows are < n
+    const unsigned* idx = nullptr;
+    if (nl > 0) {
+        hipError_t he = hipSuccess;
+        size_t sort_bytes = mesh_sort_scratch_bytes(nl, &he);
+        AQ_HIP(he);
+        if (n > 1) {
+            sort_bytes = std::max(sort_bytes, mesh_sort_rows_scratch_bytes(nl, bits, &he));
+            AQ_HIP(he);
+        }
+        for (int k = 0; k < 2; ++k) {
+            AQ_HIP(ctx->d_mkey[k].grow(nl));
+            AQ_HIP(ctx->d_midx[k].grow(nl));
+            if (n > 1) AQ_HIP(ctx->d_bkey[k].grow(nl));
+        }
+        AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
+        AQ_HIP(ctx->d_mparts.grow(grid));
+        AQ_HIP(ctx->d_bpflag.grow(grid));
+        AQ_HIP(ctx->d_bnode.grow(nl));
+        hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), nl,
+                           ctx->d_mkey[0].get(), ctx->d_midx[0].get());
+        AQ_HIP(hipGetLastError());
+        AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], nl,
+                         ctx->stream));
+        idx = ctx->d_midx[1];
+        if (n > 1) {   // the second, stable pass: by row
+            hipLaunchKernelGGL(k_mesh_batch_rowkeys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), idx, nl,
+                               ctx->d_bkey[0].get());
+            AQ_HIP(hipGetLastError());
+            AQ_HIP(mesh_sort_rows(ctx->d_msort, sort_bytes, ctx->d_bkey[0], ctx->d_bkey[1], ctx->d_midx[1], ctx->d_midx[0],
+                                  nl, bits, ctx->stream));
+            idx = ctx->d_midx[0];
+        }
+    }
+    const Leaf* lv = ctx->d_leaf;
+    unsigned* first = ctx->d_bfirst;
+    hipLaunchKernelGGL(k_mesh_batch_first, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl, nr, first);
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_batch_offsets, dim3(1), dim3(MESH_T), 0, ctx->stream, (const unsigned*)first, nr,
+                       (unsigned long long*)io->offsets);
+    AQ_HIP(hipGetLastError());
+    if (nl > 0) {
+        double2* parts = ctx->d_mparts;
+        hipLaunchKernelGGL(k_mesh_batch_expand, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl,
+                           (const unsigned*)first, (const unsigned long long*)io->offsets, io->x, io->f, io->cum,
+                           io->level, ctx->d_bnode.get(), parts, ctx->d_bpflag.get());
+        AQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_mesh_batch_scan_parts, dim3(1), dim3(MESH_T), 0, ctx->stream, parts,
+                           (const unsigned*)ctx->d_bpflag.get(), grid);
+        AQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_mesh_batch_cum, dim3(grid), dim3(MESH_T), 0, ctx->stream, nl,
+                           (const unsigned*)ctx->d_bnode.get(), io->cum, (const double2*)parts);
+        AQ_HIP(hipGetLastError());
+    }
+    if (io->area || io->accepted || io->tasks) {
+        hipLaunchKernelGGL(k_mesh_batch_finish, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, nr, (const unsigned*)first,
+                           (const unsigned long long*)io->offsets, (const double*)io->cum, io->area,
+                           (unsigned long long*)io->accepted, (unsigned long long*)io->tasks);
+        AQ_HIP(hipGetLastError());
+    }
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
 int aq_mesh_eval(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const double* d_f, const double* d_cum, size_t nq,
                  const double* d_q, double* d_out) {
     if (!ctx || n_nodes < 3) return AQ_EINVAL;
@@ -2352,6 +2525,35 @@ int aq_mesh_invert(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const doubl
                        d_y, d_out, sh, entries, top);
     AQ_HIP(hipGetLastError());
     return timing_end(ctx, ev);
+}
+
+// The batch forms: n rows x nq_per_row queries, one per lane, each on its row's slice of the batch mesh.
+using MeshBatchQueryKernel = void (*)(const unsigned long long*, const double*, const double*, const double*, size_t,
+                                      size_t, const double*, double*);
+static int mesh_queries_batch(aq_ctx* ctx, MeshBatchQueryKernel kernel, size_t n, const uint64_t* d_offsets, const double* d_x,
+                              const double* d_f, const double* d_cum, size_t nq, const double* d_q, double* d_out) {
+    if (!ctx) return AQ_EINVAL;
+    if (nq != 0 && n > (size_t)-1 / nq) return AQ_EINVAL;
+    const size_t total = n * nq;
+    if (total > 0 && (!d_offsets || !d_x || !d_f || !d_cum || !d_q || !d_out)) return AQ_EINVAL;
+    if (total == 0) return AQ_OK;
+    const size_t grid = (total + 255) / 256;
+    if (grid > 0x7fffffffull) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)d_offsets, d_x,
+                       d_f, d_cum, nq, total, d_q, d_out);
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+int aq_mesh_eval_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                       const double* d_cum, size_t nq_per_row, const double* d_q, double* d_out) {
+    return mesh_queries_batch(ctx, k_mesh_eval_batch, n, d_offsets, d_x, d_f, d_cum, nq_per_row, d_q, d_out);
+}
+
+int aq_mesh_invert_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                         const double* d_cum, size_t nq_per_row, const double* d_y, double* d_out) {
+    return mesh_queries_batch(ctx, k_mesh_invert_batch, n, d_offsets, d_x, d_f, d_cum, nq_per_row, d_y, d_out);
 }
 
 int aq_kernel_timing(aq_ctx* ctx, int enable) {

@@ -416,6 +416,26 @@ struct LeafSink {
 // LeafSink>); k_level_step<FID> has an empty pack: no argument, no leaf word, the kernel as it always was.
 __device__ __forceinline__ const LeafSink& leaf_sink(const LeafSink& s) { return s; }
 
+// Many meshes in one run (aq_integrate_mesh_batch): the frontier holds every row's records of one depth, and each
+// record carries its row -- not in Rec, which stays 32 bytes and two 16-byte loads, but in an index array beside
+// each frontier buffer (row_in beside `in`, row_out beside `out`; children inherit it). A leaf keeps its row in
+// the upper half of its depth word. theta: F_PARAM's parameter rows, gathered per record (null otherwise);
+// status: the rows' AQ_ROW_* words, which a refine at max_depth ORs AQ_ROW_DEPTH into (rare: a plain atomic).
+// k_level_step<FID, BatchSink> is the template's third form: the trailing pack again, nothing copied.
+struct BatchSink {
+    LeafSink leaf;
+    const unsigned* row_in;
+    unsigned* row_out;
+    const double* theta;
+    unsigned* status;
+    unsigned n_rows;   // a row read from the frontier is clamped below it: behind a frontier overflow the last record of
+                       // an odd capacity is one no step wrote, and its row indexes theta and status
+};
+__device__ __forceinline__ const LeafSink& leaf_sink(const BatchSink& s) { return s.leaf; }
+template <typename... Sink>
+constexpr bool is_batch_sink = (std::is_same<Sink, BatchSink>::value || ...);
+__device__ __forceinline__ const BatchSink& batch_sink(const BatchSink& s) { return s; }
+
 template <int FID, typename... Sink>
 __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ in, unsigned n_in, Rec* __restrict__ out,
                                                     unsigned* __restrict__ n_out, unsigned cap_out, double eps,
@@ -424,7 +444,9 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
                                                     const unsigned* __restrict__ n_in_dev, Sink... sink) {
     constexpr int R = LEVEL_R;
     constexpr bool MESH = sizeof...(Sink) == 1;
-    static_assert(sizeof...(Sink) <= 1, "at most one LeafSink");
+    constexpr bool BATCH = is_batch_sink<Sink...>;   // MESH with a row index per record (BatchSink)
+    static_assert(sizeof...(Sink) <= 1, "at most one LeafSink or BatchSink");
+    static_assert(BATCH || FID != F_PARAM, "theta comes with the batch form's rows");
     constexpr int LW = MESH ? LEVEL_NW : 1;
     __shared__ unsigned s_wl[2][LW];              // MESH: the waves' accepted counts of a chunk, by chunk parity
     __shared__ unsigned long long s_lbase[2];     // MESH: the chunk's first leaf slot
@@ -441,12 +463,15 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
     // record load, adding its latency to every block's
     Rec rn[R];
     bool an[R];
+    unsigned rown[BATCH ? R : 1];   // BATCH: the records' rows (an inactive lane: row 0, a valid one)
     auto load_chunk = [&](unsigned base) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const unsigned i = base + (unsigned)k * (unsigned)LEVEL_T + threadIdx.x;
             an[k] = i < n_in;
             rn[k] = an[k] ? in[i] : Rec{1.0, 1.0, 0.0, 0.0};
+            if constexpr (BATCH)
+                rown[k] = an[k] ? min(batch_sink(sink...).row_in[i], batch_sink(sink...).n_rows - 1u) : 0u;
         }
     };
     if (AQ_LEVEL_HOIST && blockIdx.x * chunk < n_in) load_chunk(blockIdx.x * chunk);
@@ -468,7 +493,18 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
             rc[k] = rn[k];
             x[k] = (rc[k].l + rc[k].r) / 2;                              // :187
         }
-        integrand_k<FID, R>(x, f, tab);                                  // :188
+        if constexpr (FID == F_PARAM) {   // every record under its own row's parameters
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                Theta<FID> th;
+#pragma unroll
+                for (int j = 0; j < param::nparams; ++j)
+                    th.v[j] = batch_sink(sink...).theta[(size_t)rown[k] * param::nparams + j];
+                f[k] = integrand<FID>(x[k], tab, th);                    // :188
+            }
+        } else {
+            integrand_k<FID, R>(x, f, tab);                              // :188
+        }
         bool refine[R];
         unsigned long long m[R];
         unsigned c[R + 1];
@@ -492,6 +528,7 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
                     ++leaves;
                 } else if (depth + 1 >= max_depth) {
                     err |= ERRB_DEPTH;
+                    if constexpr (BATCH) atomicOr(&batch_sink(sink...).status[rown[k]], (unsigned)AQ_ROW_DEPTH);
                 } else {
                     refine[k] = true;
                 }
@@ -529,8 +566,9 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
             for (int k = 0; k < R; ++k) {
                 if (leaf[k]) {
                     const unsigned long long pos = loff + cl[k] + mbcnt(ml[k]);
-                    if (pos < ls.cap)
-                        ls.buf[pos] = Leaf{rc[k].l, rc[k].r, rc[k].fl, f[k], rc[k].fr, (unsigned long long)depth};
+                    unsigned long long dw = (unsigned long long)depth;
+                    if constexpr (BATCH) dw |= (unsigned long long)rown[k] << 32;
+                    if (pos < ls.cap) ls.buf[pos] = Leaf{rc[k].l, rc[k].r, rc[k].fl, f[k], rc[k].fr, dw};
                 }
             }
         }
@@ -543,6 +581,8 @@ __global__ __launch_bounds__(LEVEL_T) void k_level_step(const Rec* __restrict__ 
                 if (pos + 1 < cap_out) {
                     out[pos] = Rec{rc[k].l, x[k], rc[k].fl, f[k]};       // [l, mid]  (:192-194)
                     out[pos + 1] = Rec{x[k], rc[k].r, f[k], rc[k].fr};   // [mid, r]  (:195-197)
+                    if constexpr (BATCH)
+                        *reinterpret_cast<uint2*>(batch_sink(sink...).row_out + pos) = make_uint2(rown[k], rown[k]);
                 } else {
                     err |= ERRB_OVERFLOW;
                 }
@@ -883,17 +923,12 @@ __global__ __launch_bounds__(MESH_T) void k_mesh_cum(unsigned n, double* __restr
 // Integral from x_0 to q on a mesh (aq_mesh_eval): the trapezoid rule on the partial panel, one IEEE operation
 // per step (the file is built with -ffp-contract=off). One query per lane, a binary search over x for the last
 // node <= q among 0 .. m - 1.
-__global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, const double* __restrict__ x,
-                                                   const double* __restrict__ f, const double* __restrict__ cum,
-                                                   size_t nq, const double* __restrict__ q, double* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nq) return;
-    const double qq = q[i];
+// (one query, shared with k_mesh_eval_batch, which runs it on a row's slice)
+__device__ __forceinline__ double mesh_eval_one(unsigned long long n_nodes, const double* __restrict__ x,
+                                                const double* __restrict__ f, const double* __restrict__ cum,
+                                                double qq) {
     const unsigned long long m = n_nodes - 1;
-    if (!(qq >= x[0] && qq <= x[m])) {   // outside, or NaN
-        out[i] = __longlong_as_double(0x7ff8000000000000ll);
-        return;
-    }
+    if (!(qq >= x[0] && qq <= x[m])) return __longlong_as_double(0x7ff8000000000000ll);   // outside, or NaN
     unsigned long long lo = 0, hi = m - 1;   // x[lo] <= q; the answer is in [lo, hi]
     while (lo < hi) {
         const unsigned long long mid = lo + (hi - lo + 1) / 2;
@@ -904,7 +939,14 @@ __global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, c
     const double h = qq - xk;
     const double w = x[lo + 1] - xk;
     const double fq = fk + (f[lo + 1] - fk) * (h / w);
-    out[i] = cum[lo] + (fk + fq) * h / 2;
+    return cum[lo] + (fk + fq) * h / 2;
+}
+__global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, const double* __restrict__ x,
+                                                   const double* __restrict__ f, const double* __restrict__ cum,
+                                                   size_t nq, const double* __restrict__ q, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    out[i] = mesh_eval_one(n_nodes, x, f, cum, q[i]);
 }
 
 // The x at which the running integral reaches y (aq_mesh_invert): k = the largest index <= m - 1 with cum_k <= y,
@@ -921,6 +963,47 @@ __global__ __launch_bounds__(256) void k_mesh_eval(unsigned long long n_nodes, c
 // Either way the last three steps run on registers: the 8 nodes from lo and the one after them, loaded in one round
 // trip, are also the panel's cum_k and cum_k+1. For any cum, monotone or not, a table index stays below `entries`
 // and a node index in [0, m - 1] (loads past it are clamped to m and not looked at).
+// The steps below bit sh from `lo`, the last three on registers, and the panel's root (every instance, and
+// k_mesh_invert_batch on a row's slice): x, f, cum are the mesh's, last = m - 1, q a y inside [cum_0, cum_m].
+__device__ __forceinline__ double mesh_invert_from(unsigned long long lo, unsigned sh, unsigned long long last,
+                                                   const double* __restrict__ x, const double* __restrict__ f,
+                                                   const double* __restrict__ cum, double q) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (unsigned b = sh; b-- > 3;) {
+        const unsigned long long mid = lo + (1ull << b);
+        const double c = cum[min(mid, last)];
+        if (mid <= last && c <= q) lo = mid;
+    }
+    // steps 4, 2, 1 on v[e] = cum[lo + e], e <= rem in range. (Where fewer than three steps were left, sh < 3,
+    // the run of 8 is wider than needed and holds the answer all the same: lo <= k.)
+    const unsigned long long rem = last - lo;
+    double v[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) v[e] = cum[min(lo + e, last + 1)];
+    const bool t4 = 4 <= rem && v[4] <= q;
+    const unsigned e2 = t4 ? 6 : 2;                 // the candidates at lo + e2 - 1 .. lo + e2 + 2
+    const double a1 = t4 ? v[5] : v[1], a2 = t4 ? v[6] : v[2], a3 = t4 ? v[7] : v[3], a4 = t4 ? v[8] : v[4];
+    const bool t2 = e2 <= rem && a2 <= q;
+    const unsigned e1 = e2 + (t2 ? 1 : -1);         // ... at lo + e1, lo + e1 + 1
+    const double c1 = t2 ? a3 : a1, c2 = t2 ? a4 : a2;
+    const bool t1 = e1 <= rem && c1 <= q;
+    const unsigned long long k = lo + e1 - (t1 ? 0 : 1);
+    const double ck = t1 ? c1 : t2 ? a2 : t4 ? v[4] : v[0];
+    const double ck1 = t1 ? c2 : c1;
+    double res = nan;
+    if (ck <= q && q <= ck1) {   // (fails only where cum is not non-decreasing)
+        const double xk = x[k], fk = f[k];
+        const double w = x[k + 1] - xk;
+        const double r = q - ck;
+        const double s = (f[k + 1] - fk) / w;
+        const double disc = fmax(fk * fk + (2 * s) * r, 0.0);
+        const double den = fk + __dsqrt_rn(disc);
+        double h = r == 0 ? 0.0 : (2 * r) / den;
+        h = fmin(h, w);
+        res = xk + h;
+    }
+    return res;
+}
 template <int LOG_TAB>
 __global__ __launch_bounds__(256) void k_mesh_invert(unsigned long long n_nodes, const double* __restrict__ x,
                                                      const double* __restrict__ f, const double* __restrict__ cum,
@@ -948,41 +1031,316 @@ __global__ __launch_bounds__(256) void k_mesh_invert(unsigned long long n_nodes,
                 if (tab[j + step] <= q) j += step;
             lo = (unsigned long long)j << sh;
         }
-        for (unsigned b = sh; b-- > 3;) {
-            const unsigned long long mid = lo + (1ull << b);
-            const double c = cum[min(mid, last)];
-            if (mid <= last && c <= q) lo = mid;
-        }
-        // steps 4, 2, 1 on v[e] = cum[lo + e], e <= rem in range. (Where fewer than three steps were left, sh < 3,
-        // the run of 8 is wider than needed and holds the answer all the same: lo <= k.)
-        const unsigned long long rem = last - lo;
-        double v[9];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) v[e] = cum[min(lo + e, last + 1)];
-        const bool t4 = 4 <= rem && v[4] <= q;
-        const unsigned e2 = t4 ? 6 : 2;                 // the candidates at lo + e2 - 1 .. lo + e2 + 2
-        const double a1 = t4 ? v[5] : v[1], a2 = t4 ? v[6] : v[2], a3 = t4 ? v[7] : v[3], a4 = t4 ? v[8] : v[4];
-        const bool t2 = e2 <= rem && a2 <= q;
-        const unsigned e1 = e2 + (t2 ? 1 : -1);         // ... at lo + e1, lo + e1 + 1
-        const double c1 = t2 ? a3 : a1, c2 = t2 ? a4 : a2;
-        const bool t1 = e1 <= rem && c1 <= q;
-        const unsigned long long k = lo + e1 - (t1 ? 0 : 1);
-        const double ck = t1 ? c1 : t2 ? a2 : t4 ? v[4] : v[0];
-        const double ck1 = t1 ? c2 : c1;
-        double res = nan;
-        if (ck <= q && q <= ck1) {   // (fails only where cum is not non-decreasing)
-            const double xk = x[k], fk = f[k];
-            const double w = x[k + 1] - xk;
-            const double r = q - ck;
-            const double s = (f[k + 1] - fk) / w;
-            const double disc = fmax(fk * fk + (2 * s) * r, 0.0);
-            const double den = fk + __dsqrt_rn(disc);
-            double h = r == 0 ? 0.0 : (2 * r) / den;
-            h = fmin(h, w);
-            res = xk + h;
-        }
-        out[i] = res;
+        out[i] = mesh_invert_from(lo, sh, last, x, f, cum, q);
     }
+}
+
+// aq_mesh_eval_batch / aq_mesh_invert_batch: row i's nq queries on the slice [off[i], off[i + 1]) of a batch mesh,
+// one query per lane, the search and the arithmetic those of the single-mesh kernels (mesh_eval_one; the plain
+// instance's halving steps from sh = the bits of the row's m - 1). A row of fewer than 3 nodes answers NaN.
+__global__ __launch_bounds__(256) void k_mesh_eval_batch(const unsigned long long* __restrict__ off,
+                                                         const double* __restrict__ x, const double* __restrict__ f,
+                                                         const double* __restrict__ cum, size_t nq, size_t total,
+                                                         const double* __restrict__ q, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t row = i / nq;
+    const unsigned long long o0 = off[row], nn = off[row + 1] - o0;
+    double res = __longlong_as_double(0x7ff8000000000000ll);
+    if (nn >= 3) res = mesh_eval_one(nn, x + o0, f + o0, cum + o0, q[i]);
+    out[i] = res;
+}
+__global__ __launch_bounds__(256) void k_mesh_invert_batch(const unsigned long long* __restrict__ off,
+                                                           const double* __restrict__ x, const double* __restrict__ f,
+                                                           const double* __restrict__ cum, size_t nq, size_t total,
+                                                           const double* __restrict__ y, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t row = i / nq;
+    const unsigned long long o0 = off[row], nn = off[row + 1] - o0;
+    double res = __longlong_as_double(0x7ff8000000000000ll);
+    if (nn >= 3) {
+        const double* c = cum + o0;
+        const unsigned long long last = nn - 2;
+        const double qq = y[i];
+        if (qq >= c[0] && qq <= c[last + 1]) {
+            const unsigned sh = 64u - (unsigned)__clzll((long long)last);   // 2^sh > m - 1 (last >= 1)
+            res = mesh_invert_from(0ull, sh, last, x + o0, f + o0, c, qq);
+        }
+    }
+    out[i] = res;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Many meshes in one call (aq_integrate_mesh_batch): every row's tree in ONE frontier (k_level_step<FID,
+// BatchSink>), the leaves ordered by (row, l) -- the sort by l, then a stable sort of the rows gathered in that
+// order -- and laid out row after row:
+//   k_mesh_batch_roots    one row per thread: the domain predicate (aq_domain.h), F(a), F(b), the status word; the
+//                         valid rows' roots compacted into level 0, one ballot-aggregated atomic per wave
+//   k_mesh_batch_rowkeys  the rows of the l-sorted leaves (the second sort's keys)
+//   k_mesh_batch_first    first[i] = the first sorted leaf of row i (a lower bound per row; first[n] = leaves)
+//   k_mesh_batch_offsets  one block: offsets = the exclusive scan of nodes_i = 2 leaves_i + (leaves_i > 0)
+//   k_mesh_batch_expand   k_mesh_expand's arithmetic, leaf j of row i at node offsets[i] + 2 (j - first[i]) (8-byte
+//                         stores: a row at an odd offset has no 16-byte aligned pairs); the row's last leaf adds
+//                         the closing node; the block's SEGMENTED double-double sum: (sum since the last row head,
+//                         has a head)
+//   k_mesh_batch_scan_parts  one block: exclusive segmented scan of the block partials, in place
+//   k_mesh_batch_cum      the parked terms back, segmented block scan, cum as k_mesh_cum writes it -- every row's
+//                         prefix starts at 0 and adds that row's terms alone
+//   k_mesh_batch_finish   one row per thread: area = the row's last cum (NaN without nodes), accepted, tasks
+// The scan's tree depends on the rows' leaf counts alone (they fix every head's lane and block), so cum is
+// bit-identical from run to run.
+// ------------------------------------------------------------------------------------------------
+template <int FID>
+__global__ __launch_bounds__(256) void k_mesh_batch_roots(const double* __restrict__ a, const double* __restrict__ b,
+                                                          const double* __restrict__ theta, unsigned n,
+                                                          Rec* __restrict__ out, unsigned* __restrict__ row_out,
+                                                          unsigned* __restrict__ count0, unsigned* __restrict__ status,
+                                                          unsigned long long* __restrict__ invalid,
+                                                          const ExpPair* __restrict__ gtab) {
+    __shared__ ExpEntry tab[ftab_entries<FID>()];
+    stage_f_table<FID>(tab, gtab);
+    __syncthreads();
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    bool ok = false;
+    Rec rc{0.0, 0.0, 0.0, 0.0};
+    if (i < n) {
+        const double x = a[i], y = b[i];
+        Theta<FID> th{};
+        if constexpr (FID == F_PARAM) {
+            constexpr int NP = param::nparams;
+            double t[NP];
+#pragma unroll
+            for (int j = 0; j < NP; ++j) t[j] = theta[(size_t)i * NP + j];
+            ok = params_ok(x, y, t);
+#pragma unroll
+            for (int j = 0; j < NP; ++j) th.v[j] = t[j];
+        } else {
+            ok = bounds_ok(FID, x, y);
+        }
+        status[i] = ok ? 0u : (unsigned)AQ_ROW_INVALID;
+        if (ok) rc = Rec{x, y, integrand<FID>(x, tab, th), integrand<FID>(y, tab, th)};
+    }
+    const unsigned long long m = __ballot(ok), bad = __ballot(i < n && !ok);
+    unsigned base = 0;
+    if (lane_id() == 0) {
+        if (m != 0ull) base = atomicAdd(count0, (unsigned)__popcll(m));
+        if (bad != 0ull) atomicAdd(invalid, (unsigned long long)__popcll(bad));
+    }
+    base = __shfl(base, 0, 64);
+    if (ok) {
+        const unsigned pos = base + mbcnt(m);   // < n <= the frontier's capacity
+        out[pos] = rc;
+        row_out[pos] = i;
+    }
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_rowkeys(const Leaf* __restrict__ leaves,
+                                                               const unsigned* __restrict__ idx, unsigned n,
+                                                               unsigned* __restrict__ keys) {
+    const unsigned j = blockIdx.x * MESH_T + threadIdx.x;
+    if (j < n) keys[j] = (unsigned)(leaves[idx[j]].depth >> 32);
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_first(const Leaf* __restrict__ leaves,
+                                                             const unsigned* __restrict__ idx, unsigned n_leaves,
+                                                             unsigned n_rows, unsigned* __restrict__ first) {
+    const unsigned i = blockIdx.x * MESH_T + threadIdx.x;
+    if (i > n_rows) return;
+    unsigned lo = 0, hi = n_leaves;   // the first leaf whose row is >= i
+    while (lo < hi) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if ((unsigned)(leaves[idx[mid]].depth >> 32) < i) lo = mid + 1;
+        else hi = mid;
+    }
+    first[i] = lo;
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_offsets(const unsigned* __restrict__ first, unsigned n_rows,
+                                                               unsigned long long* __restrict__ offsets) {
+    __shared__ unsigned long long s_sum[MESH_T];
+    const unsigned per = (n_rows + MESH_T - 1) / MESH_T;
+    const unsigned r0 = min(threadIdx.x * per, n_rows), r1 = min(r0 + per, n_rows);
+    unsigned long long sum = 0;
+    for (unsigned i = r0; i < r1; ++i) {
+        const unsigned lv = first[i + 1] - first[i];
+        sum += 2ull * lv + (lv ? 1ull : 0ull);
+    }
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    unsigned long long pre = 0;
+    for (unsigned t = 0; t < threadIdx.x; ++t) pre += s_sum[t];
+    for (unsigned i = r0; i < r1; ++i) {
+        const unsigned lv = first[i + 1] - first[i];
+        offsets[i] = pre;
+        pre += 2ull * lv + (lv ? 1ull : 0ull);
+    }
+    if (threadIdx.x == MESH_T - 1) offsets[n_rows] = pre;   // (the last share ends at n_rows, empty or not)
+}
+
+// mesh_block_scan with head flags: an inclusive scan of (value, flag) under (v1, f1) + (v2, f2) = (f2 ? v2 : v1 + v2,
+// f1 | f2) -- a lane's result is the double-double sum from the last head at or before it (or from the block's first
+// lane), its flag whether the block has such a head; `tot` receives the block's pair.
+__device__ __forceinline__ void mesh_block_scan_seg(double& hi, double& lo, bool& flag, double& tot_hi, double& tot_lo,
+                                                    bool& tot_flag) {
+    __shared__ double s_h[MESH_NW], s_l[MESH_NW];
+    __shared__ unsigned s_f[MESH_NW];
+    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
+    unsigned fl = flag ? 1u : 0u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double h2 = __shfl_up(hi, o, 64), l2 = __shfl_up(lo, o, 64);
+        const unsigned f2 = __shfl_up(fl, o, 64);
+        if (lane >= (unsigned)o) {
+            if (!fl) dd_add_dd(hi, lo, h2, l2);
+            fl |= f2;
+        }
+    }
+    if (lane == 63) { s_h[w] = hi; s_l[w] = lo; s_f[w] = fl; }
+    __syncthreads();
+    double ph = 0.0, pl = 0.0;   // the waves before this one, in order
+    unsigned pf = 0u, tf = 0u;
+    tot_hi = 0.0; tot_lo = 0.0;
+    for (unsigned v = 0; v < (unsigned)MESH_NW; ++v) {
+        if (v == w) { ph = tot_hi; pl = tot_lo; pf = tf; }
+        if (s_f[v]) { tot_hi = s_h[v]; tot_lo = s_l[v]; }
+        else dd_add_dd(tot_hi, tot_lo, s_h[v], s_l[v]);
+        tf |= s_f[v];
+    }
+    if (!fl) {
+        dd_add_dd(ph, pl, hi, lo);
+        hi = ph; lo = pl;
+    }
+    flag = (fl | pf) != 0u;
+    tot_flag = tf != 0u;
+    __syncthreads();   // s_h / s_l / s_f may be written again
+}
+
+constexpr unsigned MESH_HEAD = 0x80000000u;   // node word of a sorted leaf: its first node (< 2^31) | its row's head bit
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_expand(const Leaf* __restrict__ leaves,
+                                                              const unsigned* __restrict__ idx, unsigned n,
+                                                              const unsigned* __restrict__ first,
+                                                              const unsigned long long* __restrict__ offsets,
+                                                              double* __restrict__ x, double* __restrict__ f,
+                                                              double* __restrict__ cum, unsigned char* __restrict__ level,
+                                                              unsigned* __restrict__ node_of, double2* __restrict__ parts,
+                                                              unsigned* __restrict__ pflag) {
+    const unsigned j = blockIdx.x * MESH_T + threadIdx.x;
+    double hi = 0.0, lo = 0.0;
+    bool head = false;
+    if (j < n) {
+        const Leaf lf = leaves[idx[j]];
+        const unsigned row = (unsigned)(lf.depth >> 32);
+        const unsigned jr = j - first[row];
+        const size_t k = (size_t)offsets[row] + 2 * (size_t)jr;
+        head = jr == 0;
+        const double mid = (lf.l + lf.r) / 2;                          // :187
+        const double larea = (lf.fl + lf.fmid) * (mid - lf.l) / 2;     // :189
+        const double rarea = (lf.fmid + lf.fr) * (lf.r - mid) / 2;     // :190
+        hi = larea + rarea;                                            // :199
+        x[k] = lf.l; x[k + 1] = mid;
+        f[k] = lf.fl; f[k + 1] = lf.fmid;
+        cum[k] = hi; cum[k + 1] = larea;
+        if (level) {
+            level[k] = (unsigned char)lf.depth;
+            level[k + 1] = (unsigned char)lf.depth;
+        }
+        if (j + 1 == first[row + 1]) {   // the row's closing node (its cum: k_mesh_batch_cum)
+            x[k + 2] = lf.r;
+            f[k + 2] = lf.fr;
+        }
+        node_of[j] = (unsigned)k | (head ? MESH_HEAD : 0u);
+    }
+    double th, tl;
+    bool tf;
+    mesh_block_scan_seg(hi, lo, head, th, tl, tf);
+    if (threadIdx.x == 0) {
+        parts[blockIdx.x] = make_double2(th, tl);
+        pflag[blockIdx.x] = tf ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_scan_parts(double2* __restrict__ parts,
+                                                                  const unsigned* __restrict__ pflag, unsigned nparts) {
+    // thread t owns the contiguous share [t * per, (t + 1) * per)
+    const unsigned per = (nparts + MESH_T - 1) / MESH_T;
+    const unsigned b0 = min(threadIdx.x * per, nparts), b1 = min(b0 + per, nparts);
+    double hi = 0.0, lo = 0.0;
+    bool fl = false;
+    for (unsigned i = b0; i < b1; ++i) {
+        const double2 p = parts[i];
+        if (pflag[i]) { hi = p.x; lo = p.y; fl = true; }
+        else dd_add_dd(hi, lo, p.x, p.y);
+    }
+    double th, tl;
+    bool tf;
+    mesh_block_scan_seg(hi, lo, fl, th, tl, tf);
+    // the share's carry-in is the inclusive pair of the thread before (nothing is subtracted)
+    __shared__ double s_eh[MESH_T], s_el[MESH_T];
+    s_eh[threadIdx.x] = hi; s_el[threadIdx.x] = lo;
+    __syncthreads();
+    double eh = 0.0, el = 0.0;
+    if (threadIdx.x > 0) { eh = s_eh[threadIdx.x - 1]; el = s_el[threadIdx.x - 1]; }
+    for (unsigned i = b0; i < b1; ++i) {
+        const double2 p = parts[i];
+        parts[i] = make_double2(eh, el);   // the sum since the last head before block i
+        if (pflag[i]) { eh = p.x; el = p.y; }
+        else dd_add_dd(eh, el, p.x, p.y);
+    }
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_cum(unsigned n, const unsigned* __restrict__ node_of,
+                                                           double* __restrict__ cum, const double2* __restrict__ parts) {
+    const unsigned j = blockIdx.x * MESH_T + threadIdx.x;
+    double area = 0.0, larea = 0.0;
+    size_t k = 0;
+    bool head = false, last = false;
+    if (j < n) {
+        const unsigned w = node_of[j];
+        k = (size_t)(w & ~MESH_HEAD);
+        head = (w & MESH_HEAD) != 0u;
+        last = j + 1 == n || (node_of[j + 1] & MESH_HEAD) != 0u;
+        area = cum[k]; larea = cum[k + 1];
+    }
+    double hi = area, lo = 0.0, th, tl;
+    bool fl = head, tf;
+    mesh_block_scan_seg(hi, lo, fl, th, tl, tf);
+    const double2 base = parts[blockIdx.x];
+    // P_{j+1} within the row: this block's segment sum, behind the blocks before where no head precedes the lane
+    double ih = hi, il = lo;
+    if (!fl) {
+        ih = base.x; il = base.y;
+        dd_add_dd(ih, il, hi, lo);
+    }
+    __shared__ double s_ih[MESH_T], s_il[MESH_T];   // every lane's inclusive prefix, for the lane after it
+    s_ih[threadIdx.x] = ih; s_il[threadIdx.x] = il;
+    __syncthreads();
+    if (j >= n) return;
+    // P_j: 0 at a row's head, else the inclusive prefix of the lane before (the block's first lane: the base alone)
+    double ph = 0.0, pl = 0.0;
+    if (!head) {
+        if (threadIdx.x > 0) { ph = s_ih[threadIdx.x - 1]; pl = s_il[threadIdx.x - 1]; }
+        else { ph = base.x; pl = base.y; }
+    }
+    double mh = ph, ml = pl;
+    dd_add_dd(mh, ml, larea, 0.0);
+    cum[k] = ph + pl;
+    cum[k + 1] = mh + ml;
+    if (last) cum[k + 2] = ih + il;
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_batch_finish(unsigned n_rows, const unsigned* __restrict__ first,
+                                                              const unsigned long long* __restrict__ offsets,
+                                                              const double* __restrict__ cum, double* __restrict__ area,
+                                                              unsigned long long* __restrict__ accepted,
+                                                              unsigned long long* __restrict__ tasks) {
+    const unsigned i = blockIdx.x * MESH_T + threadIdx.x;
+    if (i >= n_rows) return;
+    const unsigned long long lv = first[i + 1] - first[i];
+    if (area) area[i] = lv ? cum[offsets[i + 1] - 1] : __longlong_as_double(0x7ff8000000000000ll);
+    if (accepted) accepted[i] = lv;
+    if (tasks) tasks[i] = lv ? 2 * lv - 1 : 0ull;
 }
 
 // Gather n slots' totals into a caller device buffer as f64 [area, tasks, accepted, error] rows,
