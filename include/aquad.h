@@ -534,7 +534,8 @@ int aq_mesh_invert(aq_ctx *ctx, uint64_t n_nodes, const double *d_x, const doubl
  * context's stream, own no device memory and read nothing on the host (aq_synchronize orders the output).
  * AQ_EINVAL: a NULL ctx, or a NULL array with n * nq_per_row > 0.
  * Not covered: shards and aq_group, meshes from the persistent kernel, the CLI, a device-side retry when a
- * capacity is missed, a per-row eps, a staged-table search for very many queries per row. */
+ * capacity is missed, a staged-table search for very many queries per row. A finer mesh from this one, and with it
+ * a per-row eps, are aq_mesh_refine_batch's (below). */
 typedef struct {
     const double *a, *b;        /* DEVICE [n] */
     const double *theta;        /* DEVICE [n * aq_param_count()] row-major; non-NULL exactly for AQ_F_PARAM */
@@ -557,6 +558,59 @@ int aq_mesh_eval_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const d
                        const double *d_cum, size_t nq_per_row, const double *d_q, double *d_out);
 int aq_mesh_invert_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
                          const double *d_cum, size_t nq_per_row, const double *d_y, double *d_out);
+
+/* ---- mesh refinement: a batch mesh continued to a smaller eps ---------------------------------------
+ * aq_mesh_refine_batch takes the meshes aq_integrate_mesh_batch (or an earlier refinement) returned for n rows --
+ * d_offsets [n + 1], d_x, d_f, d_level [offsets[n]]; cum is not read -- and returns in `out` the meshes of the same
+ * rows at eps, without evaluating F again where the input already holds it. A mesh stores, bit for bit, what the
+ * task step computed for every accepted task (l, mid, r, F(l), F(mid), F(r), its depth), and the tree at eps' <= eps
+ * is a super-tree of the tree at eps, so:
+ * Retest. Every input leaf of an active row (d_active[i] != 0; d_active NULL: every row) is retested with the three
+ * area expressions of the task step and fabs((larea + rarea) - lrarea) > eps, one IEEE operation each. A leaf that
+ * passes stays a leaf. A leaf at depth d that fails contributes its two children {l, mid, F(l), F(mid)} and
+ * {mid, r, F(mid), F(r)} to the frontier of depth d + 1, and the tree goes on exactly as aq_integrate_mesh_batch
+ * walks it. Rows that are not active keep all their leaves. A row without nodes stays without nodes: AQ_ROW_INVALID
+ * in status, area NaN, accepted = tasks = 0.
+ * Result. For active rows and eps no larger than the eps the input was built with, `out` is the mesh
+ * aq_integrate_mesh_batch defines at eps: offsets, x, f and level bit for bit, every cum value within that call's
+ * bound, and cum bit for bit as well whenever that call would hold the same leaves in every row (every row active).
+ * With eps at or above the input's nothing fails: the output is the input and info->evaluated == 0.
+ * out->a, out->b and out->theta are ignored; d_theta (DEVICE [n * aq_param_count()]) is non-NULL exactly for
+ * AQ_F_PARAM. The inputs must not overlap the outputs and are not validated (as the query calls do not validate
+ * theirs). Every mesh pointer is DEVICE memory of the context's device; the call blocks.
+ * info: n_nodes, leaves and tasks (= 2 * leaves - rows with nodes) of the OUTPUT meshes; evaluated = the task steps
+ * this call ran = evaluations of F = (tasks of the output trees) - (tasks of the input trees), whatever the mask;
+ * reseeded = the input leaves that failed; levels = the deepest level + 1 of the output trees; widest_level = the
+ * largest level of THIS run, the frontier_cap that suffices (roots never enter the frontier: it has no relation to n).
+ * Capacity and errors, as aq_integrate_mesh_batch: past cap_nodes the trees are walked to their end, info->n_nodes is
+ * reported and the return is AQ_EOVERFLOW; a level past frontier_cap is AQ_EOVERFLOW with n_nodes = 0; AQ_EDEPTH
+ * when a failing leaf or a later task would refine at max_depth, with AQ_ROW_DEPTH on those rows. AQ_EINVAL: a NULL
+ * ctx, info, out, offsets / x / f / cum of out, or input array (d_level among them: the depths come from it); a
+ * theta that does not go with the integrand; a bad eps, max_depth or sync_every; frontier_cap < 2; cap_nodes < 3 or
+ * > 2^31. n == 0: AQ_OK, info zeroed, nothing enqueued.
+ * Device memory. The seed buffer (36 bytes per child of a failing leaf) and the depth table are context-owned,
+ * allocated by the first such call and grown on demand; aq_ctx_device_bytes does not move before that call.
+ * aq_mesh_err_batch gives, per row of a batch mesh, Σ|d| and Σd over its leaves, d = (larea + rarea) - lrarea
+ * recomputed from the nodes, so every term is the reference's own double (:191) -- the error estimate of the _err
+ * calls, from the mesh alone. The sums are carried in double-double and rounded once: each lies within accepted_i *
+ * 2^-100 * Σ|d| of the exact sum before that rounding. The reduction's shape is fixed by the row's own leaf count
+ * (no float atomics), so a row's sums are bit-identical from run to run and in whatever batch the row sits. A row
+ * without nodes gives NaN. Either output may be NULL. The call only enqueues on the context's stream; its scratch
+ * is context-owned. AQ_EINVAL: a NULL ctx, or a NULL input with n > 0.
+ * Not covered: the single-mesh form (a batch of one row serves), shards and groups, coarsening, the CLI, a C form
+ * of the tolerance loop (Context.integrate_mesh_batch_tol drives these two calls round by round). */
+typedef struct {
+    uint64_t n_nodes, leaves, tasks;   /* of the OUTPUT meshes; tasks = 2 * leaves - rows with nodes */
+    uint64_t evaluated;                /* task steps this call ran (= evaluations of F) */
+    uint64_t reseeded;                 /* input leaves that failed the new test */
+    uint32_t levels, widest_level;     /* deepest level + 1 of the output trees; the largest level of THIS run */
+} aq_mesh_refine_info;
+int aq_mesh_refine_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                         const uint8_t *d_level, const double *d_theta, const uint8_t *d_active, double eps,
+                         int integrand, const aq_mesh_batch_io *out, uint32_t frontier_cap, int sync_every,
+                         uint64_t cap_nodes, aq_mesh_refine_info *info);
+int aq_mesh_err_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                      double *d_err_abs, double *d_err_signed);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel, and of aq_mesh_invert's kernel, on

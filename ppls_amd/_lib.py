@@ -27,6 +27,7 @@ EXPORTS = (
     "aq_integrate_batch_device", "aq_device_batch_check",
     "aq_integrate_mesh", "aq_mesh_eval", "aq_mesh_invert",
     "aq_integrate_mesh_batch", "aq_mesh_eval_batch", "aq_mesh_invert_batch",
+    "aq_mesh_refine_batch", "aq_mesh_err_batch",
 )
 
 AQ_MAX_LEVELS = 128
@@ -83,6 +84,12 @@ class aq_mesh_batch_io(ctypes.Structure):
 class aq_mesh_batch_info(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
                 ("invalid_rows", ctypes.c_uint64), ("levels", ctypes.c_uint32), ("widest_level", ctypes.c_uint32)]
+
+
+class aq_mesh_refine_info(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
+                ("evaluated", ctypes.c_uint64), ("reseeded", ctypes.c_uint64), ("levels", ctypes.c_uint32),
+                ("widest_level", ctypes.c_uint32)]
 
 
 _lib = None
@@ -180,6 +187,10 @@ def load(build_if_missing=True):
                                      c_int, ctypes.c_uint64, ctypes.POINTER(aq_mesh_batch_info)], c_int),
         "aq_mesh_eval_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
         "aq_mesh_invert_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp], c_int),
+        "aq_mesh_refine_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, c_dbl, c_int,
+                                  ctypes.POINTER(aq_mesh_batch_io), ctypes.c_uint32, c_int, ctypes.c_uint64,
+                                  ctypes.POINTER(aq_mesh_refine_info)], c_int),
+        "aq_mesh_err_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

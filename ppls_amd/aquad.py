@@ -87,13 +87,19 @@ class TolResult(tuple):
 # 2^63); status int32: 0, or ROW_* bits.
 DeviceBatch = collections.namedtuple("DeviceBatch", "area tasks accepted err_abs err_signed status")
 ROW_TIMEOUT, ROW_OVERFLOW, ROW_DEPTH, ROW_INVALID = 1, 2, 4, 8   # aquad.h AQ_ROW_*
+# Context.integrate_mesh_batch_tol's result: the final MeshBatch; err_abs, err_signed, eps_used (float64) and rounds
+# (int32) as torch CUDA tensors of n; converged (bool: every row met its tolerance); evaluated (the task steps of
+# all rounds together = the tasks of the final trees).
+MeshTol = collections.namedtuple("MeshTol", "mesh err_abs err_signed eps_used rounds converged evaluated")
 
 
 class MeshBatch:
     """Context.integrate_mesh_batch's result, all torch CUDA tensors: offsets (n + 1, int64) with row i's nodes at
     [offsets[i], offsets[i+1]) of x, f, cum (float64) and level (uint8), all trimmed to n_nodes; per row area
     (float64: the row's last cum, NaN for an invalid row), accepted, tasks (int64) and status (int32: 0 or ROW_*
-    bits); and the run's n_nodes, leaves, total_tasks, invalid_rows, levels, widest_level."""
+    bits); and the run's n_nodes, leaves, total_tasks, invalid_rows, levels, widest_level. It also records what it was
+    built with -- integrand, theta, eps, max_depth -- which Context.mesh_refine continues from; a mesh that
+    mesh_refine returned carries that call's eps, evaluated and reseeded as well."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -660,7 +666,8 @@ class Context:
         return MeshBatch(offsets=offsets, x=x[:m], f=f[:m], cum=cum[:m], level=level[:m], area=area, accepted=accepted,
                          tasks=tasks, status=status, n_nodes=m, leaves=int(info.leaves), total_tasks=int(info.tasks),
                          invalid_rows=int(info.invalid_rows), levels=int(info.levels),
-                         widest_level=int(info.widest_level))
+                         widest_level=int(info.widest_level), integrand=integrand, theta=theta, eps=float(eps),
+                         max_depth=int(max_depth))
 
     def _mesh_batch_queries(self, call, mesh, q, what):
         """aq_mesh_eval_batch / aq_mesh_invert_batch on checked tensors (_mesh_queries's checks and waiting): q is
@@ -711,6 +718,136 @@ class Context:
             u = u[None, :]
         return self.mesh_invert_batch(mesh, (u * mesh.area[:, None]).contiguous())
 
+
+    # -- mesh refinement: a batch mesh continued to a smaller eps, and tolerance-driven meshes --
+    def mesh_refine(self, mesh: MeshBatch, eps, active=None, cap_nodes=None, frontier_cap=1 << 22,
+                    sync_every=4) -> MeshBatch:
+        """The meshes of `mesh`'s rows at eps <= mesh.eps (aq_mesh_refine_batch): every leaf the input holds is kept or
+        split from what the mesh stores, and only the new tasks evaluate F. active: None (every row), or a bool /
+        uint8 CUDA tensor (n,): rows to refine -- the others keep their leaves. Returns a new MeshBatch (integrand,
+        theta and max_depth the input's, eps this call's) with `evaluated`, the task steps this call ran, and
+        `reseeded`, the input leaves that failed the new test; total_tasks counts the output trees. Blocks.
+        cap_nodes=None tries 4 x the input's nodes and retries once with the size an AQ_EOVERFLOW reports."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n, m_in = len(mesh), int(mesh.x.shape[0])
+        for t, what, dt in ((mesh.offsets, "mesh.offsets", torch.int64), (mesh.x, "mesh.x", torch.float64),
+                            (mesh.f, "mesh.f", torch.float64), (mesh.level, "mesh.level", torch.uint8)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dt} tensor on {dev}")
+        if mesh.f.shape[0] != m_in or mesh.level.shape[0] != m_in:
+            raise ValueError("mesh.x, mesh.f and mesh.level must have one length")
+        if active is not None:
+            if not (isinstance(active, torch.Tensor) and active.is_cuda and active.device == dev and
+                    tuple(active.shape) == (n,) and active.dtype in (torch.bool, torch.uint8)):
+                raise ValueError(f"active must be a bool or uint8 tensor of shape ({n},) on {dev}")
+            active = active.to(torch.uint8).contiguous()
+        theta, integrand, max_depth = mesh.theta, mesh.integrand, int(mesh.max_depth)
+        retry = cap_nodes is None
+        cap_nodes = max(4 * m_in, 3) if retry else int(cap_nodes)
+        if cap_nodes < 3:
+            raise ValueError("cap_nodes must be at least 3")
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        while True:
+            x, f, cum = (torch.empty(cap_nodes, dtype=torch.float64, device=dev) for _ in range(3))
+            level = torch.empty(cap_nodes, dtype=torch.uint8, device=dev)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            area = torch.empty(n, dtype=torch.float64, device=dev)
+            accepted, tasks = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2))
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            io = _lib.aq_mesh_batch_io(None, None, None, ptr(offsets), ptr(x), ptr(f), ptr(cum), ptr(level), ptr(area),
+                                       ptr(accepted), ptr(tasks), ptr(status), max_depth, 0)
+            info = _lib.aq_mesh_refine_info()
+            rc = self.L.aq_mesh_refine_batch(self._h, n, ptr(mesh.offsets), ptr(mesh.x), ptr(mesh.f), ptr(mesh.level),
+                                             ptr(theta), ptr(active), float(eps), integrand, ctypes.byref(io),
+                                             int(frontier_cap), int(sync_every), cap_nodes, ctypes.byref(info))
+            if rc == -4 and info.n_nodes:   # AQ_EOVERFLOW of cap_nodes
+                if retry:
+                    retry, cap_nodes = False, int(info.n_nodes)
+                    continue
+                e = AquadError(f"aq_mesh_refine_batch: the meshes have {info.n_nodes} nodes, cap_nodes is {cap_nodes} "
+                               f"(code {rc})", rc)
+                e.n_nodes = int(info.n_nodes)
+                raise e
+            _check(rc, "aq_mesh_refine_batch")
+            break
+        m = int(info.n_nodes)
+        return MeshBatch(offsets=offsets, x=x[:m], f=f[:m], cum=cum[:m], level=level[:m], area=area, accepted=accepted,
+                         tasks=tasks, status=status, n_nodes=m, leaves=int(info.leaves), total_tasks=int(info.tasks),
+                         invalid_rows=n - (m - 2 * int(info.leaves)), levels=int(info.levels),
+                         widest_level=int(info.widest_level), integrand=integrand, theta=theta, eps=float(eps),
+                         max_depth=max_depth, evaluated=int(info.evaluated), reseeded=int(info.reseeded))
+
+    def mesh_err(self, mesh: MeshBatch):
+        """(err_abs, err_signed): per row of a MeshBatch Σ|d| and Σd over its leaves, d = (larea + rarea) - lrarea
+        recomputed from the nodes (aq_mesh_err_batch) -- float64 CUDA tensors (n,), NaN for a row without nodes,
+        bit-identical from run to run and in whatever batch a row sits."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = len(mesh)
+        for t, what, dt in ((mesh.offsets, "mesh.offsets", torch.int64), (mesh.x, "mesh.x", torch.float64),
+                            (mesh.f, "mesh.f", torch.float64)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dt} tensor on {dev}")
+        err_abs, err_signed = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.L.aq_mesh_err_batch(self._h, n, mesh.offsets.data_ptr(), mesh.x.data_ptr(), mesh.f.data_ptr(),
+                                        err_abs.data_ptr(), err_signed.data_ptr()), "aq_mesh_err_batch")
+        self.synchronize()
+        return err_abs, err_signed
+
+    def integrate_mesh_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12,
+                                 integrand=COSH4, theta=None, max_depth=0, cap_nodes=None, frontier_cap=1 << 22,
+                                 sync_every=4) -> "MeshTol":
+        """Meshes driven by a tolerance on the result: every row refined until err_abs <= fmax(epsabs, epsrel * |area|)
+        (a tie converges, a NaN does not), with integrate_batch_tol's schedule eps_{r+1} = eps_r / shrink, one division
+        per round. Round 1 is integrate_mesh_batch at eps0; every later round is mesh_refine under the mask of the rows
+        that have not retired, so over all rounds every task of the final trees is evaluated exactly once. The test
+        runs on the device; there is one host look per round. Returns MeshTol(mesh, err_abs, err_signed, eps_used,
+        rounds, converged, evaluated): row i's mesh is the mesh at eps_used[i]; rounds[i] = r if it converged in round
+        r, -r if it retired there unconverged (then converged is False); a row outside the domain retires in round 1
+        with rounds -1 and NaN sums. The aq_tol rules give ValueError. a, b, theta as integrate_mesh_batch's."""
+        import torch
+        epsabs, epsrel, eps0, shrink = float(epsabs), float(epsrel), float(eps0), float(shrink)
+        max_rounds, max_depth = int(max_rounds), int(max_depth)
+        shrink = shrink if shrink != 0.0 else 8.0
+        max_rounds = max_rounds if max_rounds != 0 else 12
+        fin = float(np.finfo(np.float64).max)
+        if not (0.0 <= epsabs <= fin and 0.0 <= epsrel <= fin) or (epsabs == 0.0 and epsrel == 0.0):
+            raise ValueError("epsabs and epsrel must be finite and >= 0, and not both 0")
+        if not (0.0 < eps0 <= fin) or not (2.0 <= shrink <= 1024.0) or not (1 <= max_rounds <= 64):
+            raise ValueError("eps0 must be finite and > 0, shrink in [2, 1024], max_rounds in [1, 64]")
+        if not (0 <= max_depth <= _lib.AQ_MAX_LEVELS - 1):
+            raise ValueError("max_depth must be in [0, AQ_MAX_LEVELS - 1]")
+        last = eps0
+        for _ in range(max_rounds - 1):
+            last = last / shrink
+        if not last >= 2.0 ** -1022:
+            raise ValueError("the last round's eps must still be a normal number")
+        eps, r = eps0, 1
+        mesh = self.integrate_mesh_batch(a, b, eps, integrand=integrand, theta=theta, cap_nodes=cap_nodes,
+                                         frontier_cap=frontier_cap, sync_every=sync_every, max_depth=max_depth)
+        n, dev = len(mesh), mesh.area.device
+        evaluated = mesh.total_tasks
+        rounds = torch.zeros(n, dtype=torch.int32, device=dev)
+        eps_used = torch.zeros(n, dtype=torch.float64, device=dev)
+        invalid = mesh.status != 0
+        live = torch.ones(n, dtype=torch.bool, device=dev)
+        floor = torch.full((n,), epsabs, dtype=torch.float64, device=dev)
+        while True:
+            err_abs, err_signed = self.mesh_err(mesh)
+            conv = (err_abs <= torch.fmax(floor, epsrel * mesh.area.abs())) & ~invalid
+            retire = live & (conv | invalid | (r == max_rounds))
+            rounds = torch.where(retire, torch.where(conv, r, -r).to(torch.int32), rounds)
+            eps_used = torch.where(retire, torch.full_like(eps_used, eps), eps_used)
+            live = live & ~retire
+            if not bool(live.any()):   # the round's one host look
+                break
+            eps, r = eps / shrink, r + 1
+            mesh = self.mesh_refine(mesh, eps, active=live, frontier_cap=frontier_cap, sync_every=sync_every)
+            evaluated += mesh.evaluated
+        return MeshTol(mesh, err_abs, err_signed, eps_used, rounds, bool((rounds > 0).all()), evaluated)
 
     # -- tolerance-driven batch: epsabs / epsrel on the result --------------------------------
     def integrate_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12, integrand=COSH4,

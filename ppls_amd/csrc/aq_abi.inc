@@ -297,6 +297,14 @@ struct aq_ctx {
     DevBuf<unsigned> d_bstatus{&dev_bytes};         // [n] the rows' status when the caller wants none
     DevBuf<unsigned long long> d_binvalid{&dev_bytes};   // rows that failed the check (one word)
     PinBuf<unsigned long long> h_bwords;            // pinned: the leaf count and the invalid rows
+    // mesh refinement (aq_mesh_refine_batch), allocated by its first call and grown on demand; it runs in the batch's
+    // buffers above and adds:
+    DevBuf<Rec> d_rseed{&dev_bytes};                // the failing leaves' children, one segment per depth
+    DevBuf<unsigned> d_rseedrow{&dev_bytes};        // ... and their rows
+    DevBuf<unsigned> d_rtab{&dev_bytes};            // the depth table (aquad.hip REFINE_TAB_*)
+    PinBuf<unsigned> h_rtab;                        // pinned copy
+    PinBuf<unsigned long long> h_rnodes;            // pinned: the input's node count (one word)
+    DevBuf<double4> d_eparts{&dev_bytes};           // aq_mesh_err_batch's block partials (its first call)
     HostBatch batch{&dev_bytes};       // the batch front end's rings and pinned copies (grown by its calls)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
     // rows on the device beside d_bounds, and their pinned staging ring
@@ -2316,6 +2324,76 @@ int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, i
     return AQ_OK;
 }
 
+// The back half of aq_integrate_mesh_batch, which aq_mesh_refine_batch shares: the nl leaves of n rows in the context's
+// leaf buffer, in any order, sorted by (row, l) and laid out row after row (aquad.hip k_mesh_batch_*). Waits.
+static int mesh_batch_back(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, unsigned nl) {
+    const unsigned nr = (unsigned)n;
+    const unsigned grid = (nl + MESH_T - 1) / MESH_T, rgrid = (nr + 1 + MESH_T - 1) / MESH_T;
+    unsigned bits = 0;
+    while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;   // ceil(log2 n): the rows are < n
+    const unsigned* idx = nullptr;
+    if (nl > 0) {
+        hipError_t he = hipSuccess;
+        size_t sort_bytes = mesh_sort_scratch_bytes(nl, &he);
+        AQ_HIP(he);
+        if (n > 1) {
+            sort_bytes = std::max(sort_bytes, mesh_sort_rows_scratch_bytes(nl, bits, &he));
+            AQ_HIP(he);
+        }
+        for (int k = 0; k < 2; ++k) {
+            AQ_HIP(ctx->d_mkey[k].grow(nl));
+            AQ_HIP(ctx->d_midx[k].grow(nl));
+            if (n > 1) AQ_HIP(ctx->d_bkey[k].grow(nl));
+        }
+        AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
+        AQ_HIP(ctx->d_mparts.grow(grid));
+        AQ_HIP(ctx->d_bpflag.grow(grid));
+        AQ_HIP(ctx->d_bnode.grow(nl));
+        hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), nl,
+                           ctx->d_mkey[0].get(), ctx->d_midx[0].get());
+        AQ_HIP(hipGetLastError());
+        AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], nl,
+                         ctx->stream));
+        idx = ctx->d_midx[1];
+        if (n > 1) {   // the second, stable pass: by row
+            hipLaunchKernelGGL(k_mesh_batch_rowkeys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), idx, nl,
+                               ctx->d_bkey[0].get());
+            AQ_HIP(hipGetLastError());
+            AQ_HIP(mesh_sort_rows(ctx->d_msort, sort_bytes, ctx->d_bkey[0], ctx->d_bkey[1], ctx->d_midx[1], ctx->d_midx[0],
+                                  nl, bits, ctx->stream));
+            idx = ctx->d_midx[0];
+        }
+    }
+    const Leaf* lv = ctx->d_leaf;
+    unsigned* first = ctx->d_bfirst;
+    hipLaunchKernelGGL(k_mesh_batch_first, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl, nr, first);
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_batch_offsets, dim3(1), dim3(MESH_T), 0, ctx->stream, (const unsigned*)first, nr,
+                       (unsigned long long*)io->offsets);
+    AQ_HIP(hipGetLastError());
+    if (nl > 0) {
+        double2* parts = ctx->d_mparts;
+        hipLaunchKernelGGL(k_mesh_batch_expand, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl,
+                           (const unsigned*)first, (const unsigned long long*)io->offsets, io->x, io->f, io->cum,
+                           io->level, ctx->d_bnode.get(), parts, ctx->d_bpflag.get());
+        AQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_mesh_batch_scan_parts, dim3(1), dim3(MESH_T), 0, ctx->stream, parts,
+                           (const unsigned*)ctx->d_bpflag.get(), grid);
+        AQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_mesh_batch_cum, dim3(grid), dim3(MESH_T), 0, ctx->stream, nl,
+                           (const unsigned*)ctx->d_bnode.get(), io->cum, (const double2*)parts);
+        AQ_HIP(hipGetLastError());
+    }
+    if (io->area || io->accepted || io->tasks) {
+        hipLaunchKernelGGL(k_mesh_batch_finish, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, nr, (const unsigned*)first,
+                           (const unsigned long long*)io->offsets, (const double*)io->cum, io->area,
+                           (unsigned long long*)io->accepted, (unsigned long long*)io->tasks);
+        AQ_HIP(hipGetLastError());
+    }
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
 // Many meshes per call: frontier_run's loop over ONE frontier that holds every row's records of a depth (level 0:
 // the valid rows' roots, compacted by k_mesh_batch_roots; no narrow top -- level 0 is already n records wide, and a
 // small batch's few narrow levels cost a launch each as a lone mesh's levels past the top do), then the leaves
@@ -2406,70 +2484,175 @@ int aq_integrate_mesh_batch(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, d
     for (int d = 0; d < AQ_MAX_LEVELS + 2; ++d) info->widest_level = std::max(info->widest_level, (uint32_t)c[d]);
     info->n_nodes = 2 * leaves + (n - info->invalid_rows);
     if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
-    const unsigned nl = (unsigned)leaves;
-    const unsigned grid = (nl + MESH_T - 1) / MESH_T, rgrid = (nr + 1 + MESH_T - 1) / MESH_T;
-    unsigned bits = 0;
-    while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;   // ceil(log2 n): the rows are < n
-    const unsigned* idx = nullptr;
-    if (nl > 0) {
-        hipError_t he = hipSuccess;
-        size_t sort_bytes = mesh_sort_scratch_bytes(nl, &he);
-        AQ_HIP(he);
-        if (n > 1) {
-            sort_bytes = std::max(sort_bytes, mesh_sort_rows_scratch_bytes(nl, bits, &he));
-            AQ_HIP(he);
-        }
-        for (int k = 0; k < 2; ++k) {
-            AQ_HIP(ctx->d_mkey[k].grow(nl));
-            AQ_HIP(ctx->d_midx[k].grow(nl));
-            if (n > 1) AQ_HIP(ctx->d_bkey[k].grow(nl));
-        }
-        AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
-        AQ_HIP(ctx->d_mparts.grow(grid));
-        AQ_HIP(ctx->d_bpflag.grow(grid));
-        AQ_HIP(ctx->d_bnode.grow(nl));
-        hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), nl,
-                           ctx->d_mkey[0].get(), ctx->d_midx[0].get());
-        AQ_HIP(hipGetLastError());
-        AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], nl,
-                         ctx->stream));
-        idx = ctx->d_midx[1];
-        if (n > 1) {   // the second, stable pass: by row
-            hipLaunchKernelGGL(k_mesh_batch_rowkeys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), idx, nl,
-                               ctx->d_bkey[0].get());
-            AQ_HIP(hipGetLastError());
-            AQ_HIP(mesh_sort_rows(ctx->d_msort, sort_bytes, ctx->d_bkey[0], ctx->d_bkey[1], ctx->d_midx[1], ctx->d_midx[0],
-                                  nl, bits, ctx->stream));
-            idx = ctx->d_midx[0];
-        }
-    }
-    const Leaf* lv = ctx->d_leaf;
-    unsigned* first = ctx->d_bfirst;
-    hipLaunchKernelGGL(k_mesh_batch_first, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl, nr, first);
+    return mesh_batch_back(ctx, n, io, (unsigned)leaves);
+}
+
+// A batch mesh continued to a smaller eps: aq_integrate_mesh_batch with its roots kernel replaced by the retest of
+// the input's leaves (aquad.hip k_mesh_refine_*). The survivors go straight to the leaf buffer; the failing leaves'
+// children wait in the seed buffer, one segment per depth, and join the frontier of their depth just before that
+// depth's step. The loop starts at the first depth that has seeds and ends at an empty level only when no deeper
+// segment is left. Two host looks before the loop: the input's node count, then the per-depth counts.
+int aq_mesh_refine_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                         const uint8_t* d_level, const double* d_theta, const uint8_t* d_active, double eps, int integrand,
+                         const aq_mesh_batch_io* out, uint32_t frontier_cap, int sync_every, uint64_t cap_nodes,
+                         aq_mesh_refine_info* info) {
+    if (!ctx || !out || !info || !out->offsets || !out->x || !out->f || !out->cum) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_x || !d_f || !d_level)) return AQ_EINVAL;
+    if (!theta_ok(integrand, d_theta)) return AQ_EINVAL;
+    if (!(eps >= 0.0) || out->max_depth < 0 || out->max_depth > AQ_MAX_LEVELS - 1 || sync_every < 1) return AQ_EINVAL;
+    if (frontier_cap < 2 || n > 0x7fffffffull) return AQ_EINVAL;
+    if (cap_nodes < 3 || cap_nodes > (1ull << 31)) return AQ_EINVAL;
+    *info = aq_mesh_refine_info{};
+    if (n == 0) return AQ_OK;
+    AQ_HIP(hipSetDevice(ctx->device));
+    const int max_depth = out->max_depth ? out->max_depth : AQ_DEFAULT_MAX_DEPTH;
+    const uint32_t cap = frontier_cap;
+    const unsigned nr = (unsigned)n;
+    const size_t cap_leaves = (size_t)(cap_nodes / 2);
+    int rc;
+    if ((rc = ensure_front(ctx, cap))) return rc;
+    for (int k = 0; k < 2; ++k) AQ_HIP(ctx->d_brow[k].grow(cap));
+    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
+    AQ_HIP(ctx->d_leafcnt.grow(1));
+    AQ_HIP(ctx->d_binvalid.grow(1));
+    AQ_HIP(ctx->d_bfirst.grow(n + 1));
+    if (!out->status) AQ_HIP(ctx->d_bstatus.grow(n));
+    AQ_HIP(ctx->d_facc.grow(8));
+    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
+    AQ_HIP(ctx->h_facc.grow(8));
+    AQ_HIP(ctx->h_bwords.grow(2));
+    AQ_HIP(ctx->d_rtab.grow(REFINE_TAB_WORDS));
+    AQ_HIP(ctx->h_rtab.grow(REFINE_TAB_WORDS));
+    AQ_HIP(ctx->h_rnodes.grow(1));
+    unsigned* cnt = ctx->d_count;
+    double* acc = ctx->d_facc;
+    unsigned* tab = ctx->d_rtab;
+    unsigned* status = out->status ? out->status : ctx->d_bstatus.get();
+    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
+    unsigned* row[2] = {ctx->d_brow[0].get(), ctx->d_brow[1].get()};
+    AQ_HIP(hipMemcpyAsync(ctx->h_rnodes, d_offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
+    AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
+    AQ_HIP(hipMemsetAsync(tab, 0, sizeof(unsigned) * REFINE_TAB_WORDS, ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_mesh_refine_rows, dim3((nr + REFINE_T - 1) / REFINE_T), dim3(REFINE_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, nr, status, ctx->d_binvalid.get());
     AQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_mesh_batch_offsets, dim3(1), dim3(MESH_T), 0, ctx->stream, (const unsigned*)first, nr,
-                       (unsigned long long*)io->offsets);
-    AQ_HIP(hipGetLastError());
-    if (nl > 0) {
-        double2* parts = ctx->d_mparts;
-        hipLaunchKernelGGL(k_mesh_batch_expand, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl,
-                           (const unsigned*)first, (const unsigned long long*)io->offsets, io->x, io->f, io->cum,
-                           io->level, ctx->d_bnode.get(), parts, ctx->d_bpflag.get());
-        AQ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_mesh_batch_scan_parts, dim3(1), dim3(MESH_T), 0, ctx->stream, parts,
-                           (const unsigned*)ctx->d_bpflag.get(), grid);
-        AQ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_mesh_batch_cum, dim3(grid), dim3(MESH_T), 0, ctx->stream, nl,
-                           (const unsigned*)ctx->d_bnode.get(), io->cum, (const double2*)parts);
+    AQ_HIP(hipStreamSynchronize(ctx->stream));   // the first look: the input's nodes
+    const unsigned long long m_in = ctx->h_rnodes[0];
+    if (m_in > (1ull << 31)) return AQ_EINVAL;
+    const RefineIn in{(const unsigned long long*)d_offsets, d_x, d_f, d_level, d_active, nr, m_in, eps, max_depth};
+    const unsigned cgrid = (unsigned)((m_in + REFINE_T - 1) / REFINE_T);
+    const LeafSink lsink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves};
+    if (cgrid) {
+        hipLaunchKernelGGL(k_mesh_refine_classify, dim3(cgrid), dim3(REFINE_T), 0, ctx->stream, in, lsink, status, tab);
         AQ_HIP(hipGetLastError());
     }
-    if (io->area || io->accepted || io->tasks) {
-        hipLaunchKernelGGL(k_mesh_batch_finish, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, nr, (const unsigned*)first,
-                           (const unsigned long long*)io->offsets, (const double*)io->cum, io->area,
-                           (unsigned long long*)io->accepted, (unsigned long long*)io->tasks);
+    AQ_HIP(hipMemcpyAsync(ctx->h_rtab, tab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));   // the second look: the failing leaves by depth
+    unsigned long long seg[AQ_MAX_LEVELS + 1];   // the seed records of depth e are [seg[e - 1], seg[e])
+    int first_depth = -1, last_depth = -1;       // the first and the last depth that has seeds
+    unsigned long long pre = 0;
+    for (int d = 0; d < AQ_MAX_LEVELS; ++d) {    // the children of the failing leaves of depth d: depth d + 1
+        seg[d] = 2 * pre;
+        if (ctx->h_rtab[d]) {
+            if (first_depth < 0) first_depth = d + 1;
+            last_depth = d + 1;
+        }
+        pre += ctx->h_rtab[d];
+    }
+    seg[AQ_MAX_LEVELS] = 2 * pre;
+    const unsigned long long n_seed = 2 * pre;   // <= the input's nodes <= 2^31
+    const unsigned deep_fail = ctx->h_rtab[REFINE_TAB_DEPTHFAIL];
+    info->reseeded = pre + deep_fail;
+    auto seeds_of = [&](int depth) -> unsigned long long {   // records that join the frontier of `depth`
+        return depth >= 1 && depth <= AQ_MAX_LEVELS ? seg[depth] - seg[depth - 1] : 0ull;
+    };
+    if (n_seed) {
+        AQ_HIP(ctx->d_rseed.grow(n_seed));
+        AQ_HIP(ctx->d_rseedrow.grow(n_seed));
+        hipLaunchKernelGGL(k_mesh_refine_seed, dim3(cgrid), dim3(REFINE_T), 0, ctx->stream, in, tab, ctx->d_rseed.get(),
+                           ctx->d_rseedrow.get(), n_seed);
         AQ_HIP(hipGetLastError());
     }
+    const bool defer0 = ctx->defer_fold;
+    ctx->defer_fold = true;
+    int depth = first_depth < 0 ? 0 : first_depth, since = 0;
+    unsigned long long bound = 0;   // the children the step before may have appended
+    rc = AQ_OK;
+    while (first_depth >= 0 && depth <= max_depth && depth < AQ_MAX_LEVELS) {
+        const unsigned long long ns = seeds_of(depth);
+        if (ns) {
+            hipLaunchKernelGGL(k_mesh_refine_append, dim3((unsigned)((ns + REFINE_APPEND - 1) / REFINE_APPEND)), dim3(256), 0,
+                               ctx->stream, (const Rec*)(ctx->d_rseed.get() + seg[depth - 1]),
+                               (const unsigned*)(ctx->d_rseedrow.get() + seg[depth - 1]), (unsigned)ns,
+                               (Rec*)buf[depth & 1], row[depth & 1], cnt + depth, cap, tab + REFINE_TAB_ERR);
+            if (hipGetLastError() != hipSuccess) { rc = AQ_EHIP; break; }   // (leaves the loop: defer_fold is put back)
+        }
+        const unsigned long long n_in = std::min<unsigned long long>(bound + ns, cap);
+        const BatchSink sink{lsink, row[depth & 1], row[(depth + 1) & 1], d_theta, status, nr};
+        rc = level_step_impl(ctx, integrand, buf[depth & 1], (uint32_t)n_in, cnt + depth, buf[(depth + 1) & 1], cap, eps,
+                             depth, max_depth, cnt + depth + 1, acc, nullptr, &sink);
+        if (rc) break;
+        ++depth;
+        bound = std::min<unsigned long long>(2 * n_in, cap);
+        if (bound == 0 && depth > last_depth) break;   // nothing can be left (known without a look)
+        if (++since == sync_every) {
+            since = 0;
+            if ((rc = fold_pending(ctx))) break;
+            AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+            AQ_HIP(hipStreamSynchronize(ctx->stream));
+            const unsigned now = ctx->h_fcount[0];
+            if (now == 0 && depth > last_depth) break;
+            if (now > cap) { rc = AQ_EOVERFLOW; break; }
+            bound = now;
+        }
+    }
+    ctx->defer_fold = defer0;
+    if (rc == AQ_OK) rc = fold_pending(ctx);
+    else (void)fold_pending(ctx);
+    AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_facc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_bwords, ctx->d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_bwords + 1, ctx->d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    AQ_HIP(hipMemcpyAsync(ctx->h_rtab, tab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipStreamSynchronize(ctx->stream));
+    if (rc) return rc;
+    const double* a = ctx->h_facc;
+    const unsigned* c = ctx->h_fcount;
+    info->evaluated = (uint64_t)a[2];
+    // a level past frontier_cap (a step's children, or the seeds behind them), or a refine at max_depth (a failing
+    // input leaf, or a later task)
+    if ((rc = err_from_bits((unsigned)a[4] | ctx->h_rtab[REFINE_TAB_ERR] | (deep_fail ? (unsigned)ERRB_DEPTH : 0u)))) return rc;
+    if (first_depth >= 0 && c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
+    const uint64_t leaves = ctx->h_bwords[0], with_nodes = n - ctx->h_bwords[1];
+    info->leaves = leaves;
+    info->tasks = 2 * leaves - with_nodes;
+    info->levels = std::max((uint32_t)a[5], (uint32_t)ctx->h_rtab[REFINE_TAB_LEVELS]);
+    for (int d = 0; d < AQ_MAX_LEVELS + 2; ++d) info->widest_level = std::max(info->widest_level, (uint32_t)c[d]);
+    info->n_nodes = 2 * leaves + with_nodes;
+    if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
+    return mesh_batch_back(ctx, n, out, (unsigned)leaves);
+}
+
+// Σ|d| and Σd of every row of a batch mesh (aquad.hip k_mesh_err_*). Only enqueues.
+int aq_mesh_err_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                      double* d_err_abs, double* d_err_signed) {
+    if (!ctx) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_x || !d_f)) return AQ_EINVAL;
+    if (n == 0 || (!d_err_abs && !d_err_signed)) return AQ_OK;
+    if (n > 0x7fffffffull / MESH_ERR_B) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    AQ_HIP(ctx->d_eparts.grow(n * MESH_ERR_B));
+    hipLaunchKernelGGL(k_mesh_err_parts, dim3((unsigned)(n * MESH_ERR_B)), dim3(MESH_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, d_x, d_f, ctx->d_eparts.get());
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_err_finish, dim3((unsigned)((n + MESH_T - 1) / MESH_T)), dim3(MESH_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, (unsigned)n, (const double4*)ctx->d_eparts.get(), d_err_abs,
+                       d_err_signed);
+    AQ_HIP(hipGetLastError());
     return AQ_OK;
 }
 

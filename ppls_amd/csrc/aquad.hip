@@ -1343,6 +1343,232 @@ __global__ __launch_bounds__(MESH_T) void k_mesh_batch_finish(unsigned n_rows, c
     if (tasks) tasks[i] = lv ? 2 * lv - 1 : 0ull;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Mesh refinement (aq_mesh_refine_batch): a batch mesh continued to a smaller eps. A mesh keeps, bit for bit, what
+// the task step computed for every accepted task -- l, mid, r, F(l), F(mid), F(r), its depth -- so the test is
+// redone and the two children are formed without one evaluation of F:
+//   k_mesh_refine_rows      one row per thread: status = 0, or AQ_ROW_INVALID for a row without nodes (counted)
+//   k_mesh_refine_classify  one node per thread; the even nodes before a row's last are its leaves. A leaf of an
+//                           active row that fails :191 at the new eps is counted by depth (LDS histogram, one global
+//                           atomic per non-empty bin and block); every other leaf goes to the leaf buffer as
+//                           k_level_step emits one (wave ballots, one atomic per block; past the capacity: counted)
+//   k_mesh_refine_seed      the same pass again, once the host has seen the counts: the failing leaves' children
+//                           into the seed buffer, one segment per depth (the exclusive prefix of the counts), the
+//                           row beside each record; positions from a block-local count and one atomic per bin
+//   k_mesh_refine_append    before the level step of depth d: segment d behind the children the step of depth
+//                           d - 1 appended, one atomic on counts[d] per block of 1024 records
+// Then k_level_step<FID, BatchSink> walks on and the back half of aq_integrate_mesh_batch sorts by (row, l).
+// The depth table `tab` (unsigned words): [0, AQ_MAX_LEVELS) failing leaves by depth, [AQ_MAX_LEVELS, 2 AQ_MAX_LEVELS)
+// the seed pass's cursors, then the leaves that fail at max_depth, the deepest input leaf + 1, the error bits.
+// ------------------------------------------------------------------------------------------------
+constexpr int REFINE_T = 256;
+constexpr int REFINE_TAB_CURSOR = AQ_MAX_LEVELS, REFINE_TAB_DEPTHFAIL = 2 * AQ_MAX_LEVELS,
+              REFINE_TAB_LEVELS = 2 * AQ_MAX_LEVELS + 1, REFINE_TAB_ERR = 2 * AQ_MAX_LEVELS + 2,
+              REFINE_TAB_WORDS = 2 * AQ_MAX_LEVELS + 4;
+constexpr unsigned REFINE_APPEND = 1024;   // records per block of k_mesh_refine_append
+
+struct RefineIn {   // the input mesh and what it is retested with
+    const unsigned long long* off;
+    const double* x;
+    const double* f;
+    const unsigned char* level;
+    const unsigned char* active;   // null: every row
+    unsigned n_rows;
+    unsigned long long n_nodes;    // off[n_rows], read by the host
+    double eps;
+    int max_depth;
+};
+
+__global__ __launch_bounds__(REFINE_T) void k_mesh_refine_rows(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                                unsigned* __restrict__ status,
+                                                                unsigned long long* __restrict__ invalid) {
+    const unsigned i = blockIdx.x * REFINE_T + threadIdx.x;
+    const bool in = i < n_rows;
+    const bool empty = in && off[i + 1] == off[i];
+    if (in) status[i] = empty ? (unsigned)AQ_ROW_INVALID : 0u;
+    const unsigned long long bad = __ballot(empty);
+    if (lane_id() == 0 && bad != 0ull) atomicAdd(invalid, (unsigned long long)__popcll(bad));
+}
+
+// Node k of the input: false unless it is the first node of a leaf. Otherwise the leaf as k_level_step emits one
+// and whether it fails the test at in.eps (an inactive row's never does).
+__device__ __forceinline__ bool mesh_refine_leaf(const RefineIn& in, unsigned long long k, Leaf& lf, unsigned& row,
+                                                 unsigned& depth, bool& fail) {
+    if (k + 2 >= in.n_nodes) return false;
+    unsigned lo = 0, hi = in.n_rows - 1;   // the last row that starts at or before k (rows without nodes start where
+    while (lo < hi) {                      // the next one does, so it has nodes)
+        const unsigned m = lo + (hi - lo + 1) / 2;
+        if (in.off[m] <= k) lo = m;
+        else hi = m - 1;
+    }
+    const unsigned long long o0 = in.off[lo], o1 = in.off[lo + 1];
+    if (k < o0 || ((k - o0) & 1ull) != 0ull || k + 2 >= o1) return false;
+    row = lo;
+    depth = in.level[k];
+    const double mid = in.x[k + 1];
+    lf = Leaf{in.x[k], in.x[k + 2], in.f[k], in.f[k + 1], in.f[k + 2], (unsigned long long)depth | ((unsigned long long)lo << 32)};
+    const double lrarea = (lf.fl + lf.fr) * (lf.r - lf.l) / 2;       // :185
+    const double larea = (lf.fl + lf.fmid) * (mid - lf.l) / 2;       // :189
+    const double rarea = (lf.fmid + lf.fr) * (lf.r - mid) / 2;       // :190
+    fail = (!in.active || in.active[lo] != 0) && fabs((larea + rarea) - lrarea) > in.eps;   // :191
+    return true;
+}
+
+__global__ __launch_bounds__(REFINE_T) void k_mesh_refine_classify(RefineIn in, LeafSink sink, unsigned* __restrict__ status,
+                                                                    unsigned* __restrict__ tab) {
+    __shared__ unsigned s_hist[AQ_MAX_LEVELS];
+    __shared__ unsigned s_wl[REFINE_T / 64], s_deep, s_levels;
+    __shared__ unsigned long long s_lbase;
+    if (threadIdx.x < AQ_MAX_LEVELS) s_hist[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) { s_deep = 0u; s_levels = 0u; }
+    __syncthreads();
+    const unsigned long long k = (unsigned long long)blockIdx.x * REFINE_T + threadIdx.x;
+    Leaf lf{};
+    unsigned row = 0, depth = 0;
+    bool fail = false;
+    const bool leaf = mesh_refine_leaf(in, k, lf, row, depth, fail);
+    const bool keep = leaf && !fail;
+    if (leaf) {
+        atomicMax(&s_levels, depth + 1u);
+        if (fail) {
+            if ((int)depth + 1 >= in.max_depth) {   // (so a counted depth is below AQ_MAX_LEVELS - 2)
+                atomicOr(&status[row], (unsigned)AQ_ROW_DEPTH);
+                atomicAdd(&s_deep, 1u);
+            } else {
+                atomicAdd(&s_hist[depth], 1u);
+            }
+        }
+    }
+    const unsigned long long mk = __ballot(keep);
+    const unsigned w = threadIdx.x >> 6;
+    if (lane_id() == 0) s_wl[w] = (unsigned)__popcll(mk);
+    __syncthreads();
+    if (threadIdx.x == 0) {   // one atomic for the block's leaves (64-bit: the count goes on past the capacity)
+        unsigned tot = 0;
+        for (int v = 0; v < REFINE_T / 64; ++v) tot += s_wl[v];
+        s_lbase = tot ? atomicAdd(sink.count, (unsigned long long)tot) : 0ull;
+        if (s_deep) atomicAdd(&tab[REFINE_TAB_DEPTHFAIL], s_deep);
+        if (s_levels) atomicMax(&tab[REFINE_TAB_LEVELS], s_levels);
+    }
+    if (threadIdx.x < AQ_MAX_LEVELS && s_hist[threadIdx.x]) atomicAdd(&tab[threadIdx.x], s_hist[threadIdx.x]);
+    __syncthreads();
+    if (keep) {
+        unsigned long long pos = s_lbase + mbcnt(mk);
+        for (unsigned v = 0; v < w; ++v) pos += s_wl[v];
+        if (pos < sink.cap) sink.buf[pos] = lf;
+    }
+}
+
+__global__ __launch_bounds__(REFINE_T) void k_mesh_refine_seed(RefineIn in, unsigned* __restrict__ tab, Rec* __restrict__ seed,
+                                                                unsigned* __restrict__ seed_row, unsigned long long seed_cap) {
+    __shared__ unsigned s_hist[AQ_MAX_LEVELS], s_base[AQ_MAX_LEVELS], s_seg[AQ_MAX_LEVELS];
+    if (threadIdx.x < AQ_MAX_LEVELS) s_hist[threadIdx.x] = 0u;
+    if (threadIdx.x == REFINE_T - 1) {   // the segments: the exclusive prefix of the counts
+        unsigned pre = 0;
+        for (int d = 0; d < AQ_MAX_LEVELS; ++d) { s_seg[d] = pre; pre += tab[d]; }
+    }
+    __syncthreads();
+    const unsigned long long k = (unsigned long long)blockIdx.x * REFINE_T + threadIdx.x;
+    Leaf lf{};
+    unsigned row = 0, depth = 0, rank = 0;
+    bool fail = false;
+    const bool seeds = mesh_refine_leaf(in, k, lf, row, depth, fail) && fail && (int)depth + 1 < in.max_depth;
+    if (seeds) rank = atomicAdd(&s_hist[depth], 1u);
+    __syncthreads();
+    if (threadIdx.x < AQ_MAX_LEVELS && s_hist[threadIdx.x])
+        s_base[threadIdx.x] = atomicAdd(&tab[REFINE_TAB_CURSOR + threadIdx.x], s_hist[threadIdx.x]);
+    __syncthreads();
+    if (seeds) {
+        const unsigned long long p = 2ull * ((unsigned long long)s_seg[depth] + s_base[depth] + rank);
+        if (p + 1 < seed_cap) {   // (always, for an input that did not change between the two passes)
+            const double mid = in.x[k + 1];
+            seed[p] = Rec{lf.l, mid, lf.fl, lf.fmid};       // [l, mid]  (:192-194)
+            seed[p + 1] = Rec{mid, lf.r, lf.fmid, lf.fr};   // [mid, r]  (:195-197)
+            seed_row[p] = row;
+            seed_row[p + 1] = row;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_refine_append(const Rec* __restrict__ seed, const unsigned* __restrict__ seed_row,
+                                                            unsigned n, Rec* __restrict__ out, unsigned* __restrict__ row_out,
+                                                            unsigned* __restrict__ count, unsigned cap,
+                                                            unsigned* __restrict__ err) {
+    __shared__ unsigned s_base;
+    const unsigned first = blockIdx.x * REFINE_APPEND;
+    if (threadIdx.x == 0) s_base = atomicAdd(count, min(REFINE_APPEND, n - first));
+    __syncthreads();
+    bool over = false;
+    for (unsigned i = first + threadIdx.x; i < min(first + REFINE_APPEND, n); i += 256u) {
+        const unsigned pos = s_base + (i - first);
+        if (pos < cap && pos >= s_base) {
+            out[pos] = seed[i];
+            row_out[pos] = seed_row[i];
+        } else {
+            over = true;
+        }
+    }
+    if (over) atomicOr(err, (unsigned)ERRB_OVERFLOW);
+}
+
+// aq_mesh_err_batch: per row Σ|d| and Σd over its leaves, d = (larea + rarea) - lrarea recomputed from the nodes
+// (:185-191), carried in double-double. The reduction's shape is fixed by the row's own leaf count: block (i, b) of
+// MESH_ERR_B takes the row's chunks of MESH_T leaves c = b, b + MESH_ERR_B, ... from the ROW's first leaf -- a thread
+// its leaves in order, the wave's lanes a butterfly, the waves in order -- and k_mesh_err_finish adds a row's
+// partials in block order and rounds once. So a row's sums are the same bits in any batch, at any offset.
+constexpr int MESH_ERR_B = 8;
+__global__ __launch_bounds__(MESH_T) void k_mesh_err_parts(const unsigned long long* __restrict__ off,
+                                                           const double* __restrict__ x, const double* __restrict__ f,
+                                                           double4* __restrict__ parts) {
+    __shared__ double s_v[MESH_NW][4];
+    const unsigned row = blockIdx.x / MESH_ERR_B, b = blockIdx.x % MESH_ERR_B;
+    const unsigned long long o0 = off[row], o1 = off[row + 1];
+    const unsigned long long nn = o1 > o0 ? o1 - o0 : 0ull, leaves = nn >= 3 ? (nn - 1) / 2 : 0ull;
+    double ah = 0.0, al = 0.0, sh = 0.0, sl = 0.0;
+    for (unsigned long long j = (unsigned long long)b * MESH_T + threadIdx.x; j < leaves;
+         j += (unsigned long long)MESH_ERR_B * MESH_T) {
+        const double* xs = x + o0 + 2 * j;
+        const double* fs = f + o0 + 2 * j;
+        const double l = xs[0], mid = xs[1], r = xs[2], fl = fs[0], fmid = fs[1], fr = fs[2];
+        const double lrarea = (fl + fr) * (r - l) / 2;       // :185
+        const double larea = (fl + fmid) * (mid - l) / 2;    // :189
+        const double rarea = (fmid + fr) * (r - mid) / 2;    // :190
+        const double d = (larea + rarea) - lrarea;           // :191
+        dd_add(ah, al, fabs(d));
+        dd_add(sh, sl, d);
+    }
+    wave_sum_dd(ah, al);
+    wave_sum_dd(sh, sl);
+    const unsigned w = threadIdx.x >> 6;
+    if (lane_id() == 0) { s_v[w][0] = ah; s_v[w][1] = al; s_v[w][2] = sh; s_v[w][3] = sl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double AH = 0.0, AL = 0.0, SH = 0.0, SL = 0.0;
+        for (int v = 0; v < MESH_NW; ++v) {
+            dd_add_dd(AH, AL, s_v[v][0], s_v[v][1]);
+            dd_add_dd(SH, SL, s_v[v][2], s_v[v][3]);
+        }
+        parts[blockIdx.x] = make_double4(AH, AL, SH, SL);
+    }
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_err_finish(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                            const double4* __restrict__ parts, double* __restrict__ err_abs,
+                                                            double* __restrict__ err_signed) {
+    const unsigned i = blockIdx.x * MESH_T + threadIdx.x;
+    if (i >= n_rows) return;
+    double AH = 0.0, AL = 0.0, SH = 0.0, SL = 0.0;
+    for (int b = 0; b < MESH_ERR_B; ++b) {
+        const double4 p = parts[(size_t)i * MESH_ERR_B + b];
+        dd_add_dd(AH, AL, p.x, p.y);
+        dd_add_dd(SH, SL, p.z, p.w);
+    }
+    const bool none = off[i + 1] < off[i] + 3;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (err_abs) err_abs[i] = none ? nan : AH + AL;
+    if (err_signed) err_signed[i] = none ? nan : SH + SL;
+}
+
 // Gather n slots' totals into a caller device buffer as f64 [area, tasks, accepted, error] rows,
 // ready for one collective (counts are exact in f64 below 2^53). One thread per slot: the area is
 // the correctly rounded value of the slot's exact accumulator.
