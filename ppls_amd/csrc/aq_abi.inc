@@ -4,6 +4,7 @@
 #include "aq_host_args.h"   // the argument rules and the chunk schedule (no HIP: tests/test_host_args.py)
 #include "aq_batch_plan.h"  // the batch pipelines, host and device-resident: steps, streams, events (no HIP:
                             // tests/test_batch_plan.py, tests/test_device_batch_plan.py)
+#include "aq_frontier_walk.h"   // the frontier engine's host loop (no HIP: tests/test_frontier_walk.py)
 #include "aq_host_mem.h"    // owning device / pinned buffers, events, streams
 
 using namespace aq;
@@ -228,6 +229,105 @@ struct TolBufs {
     }
 };
 
+// The frontier engine's buffers: the two frontier buffers a level step reads and writes in turn, the records per
+// depth (allocated at create: aq_integrate_levels counts there too), and a walk's accumulator (walk_run), with the
+// pinned copies of the last two.
+struct FrontBufs {
+    unsigned long long* const bytes;   // the counter the device buffers count in (aq_ctx::dev_bytes)
+    DevBuf<Rec> d_rec[2] = {DevBuf<Rec>{bytes}, DevBuf<Rec>{bytes}};   // both of one size, or neither
+    DevBuf<unsigned> d_count{bytes};   // [AQ_MAX_LEVELS + 2]
+    PinBuf<unsigned> h_count;
+    DevBuf<double> d_acc{bytes};       // 8 doubles (k_level_fold's layout)
+    PinBuf<double> h_acc;
+
+    // The two frontier buffers hold at least cap records each. They only grow; a failed allocation leaves
+    // neither, so the two always hold the same count and no caller launches on half a pair.
+    int ensure_front(size_t cap) {
+        if (d_rec[0].grow(cap) == hipSuccess && d_rec[1].grow(cap) == hipSuccess) return AQ_OK;
+        d_rec[0].reset();
+        d_rec[1].reset();
+        fprintf(stderr, "aquad: no device memory for two frontier buffers of %zu records\n", cap);
+        return AQ_EHIP;
+    }
+    // ... and what a walk over them needs beside
+    int ensure_walk(size_t cap) {
+        if (int rc = ensure_front(cap)) return rc;
+        AQ_HIP(d_acc.grow(8));
+        AQ_HIP(h_count.grow(AQ_MAX_LEVELS + 2));
+        AQ_HIP(h_acc.grow(8));
+        return AQ_OK;
+    }
+};
+
+// The accepted mesh's buffers, each allocated by the first call that needs it and grown on demand (a context that
+// made no such call holds none: aq_ctx_device_bytes does not move until then). The batch of meshes runs in the
+// single mesh's leaf, sort and partial arrays and adds its own; refinement runs in the batch's and adds its own.
+struct MeshBufs {
+    unsigned long long* const bytes;   // the counter the device buffers count in (aq_ctx::dev_bytes)
+    // the single mesh (aq_integrate_mesh)
+    DevBuf<Leaf> d_leaf{bytes};                    // leaf records in schedule order
+    DevBuf<unsigned long long> d_leafcnt{bytes};   // accepted tasks counted by the emitting kernels (one word)
+    DevBuf<double> d_mkey[2] = {DevBuf<double>{bytes}, DevBuf<double>{bytes}};       // sort keys in / out
+    DevBuf<unsigned> d_midx[2] = {DevBuf<unsigned>{bytes}, DevBuf<unsigned>{bytes}}; // leaf indices in / out
+    DevBuf<unsigned char> d_msort{bytes};          // the sort's scratch
+    DevBuf<double2> d_mparts{bytes};               // the scan's block partials
+    // the batch of meshes (aq_integrate_mesh_batch)
+    DevBuf<unsigned> d_brow[2] = {DevBuf<unsigned>{bytes}, DevBuf<unsigned>{bytes}};   // the frontier records' rows
+    DevBuf<unsigned> d_bkey[2] = {DevBuf<unsigned>{bytes}, DevBuf<unsigned>{bytes}};   // the second sort's keys in / out
+    DevBuf<unsigned> d_bfirst{bytes};              // [n + 1] every row's first sorted leaf
+    DevBuf<unsigned> d_bnode{bytes};               // a sorted leaf's first node | its row's head bit
+    DevBuf<unsigned> d_bpflag{bytes};              // the segmented scan's "block has a head"
+    DevBuf<unsigned> d_bstatus{bytes};             // [n] the rows' status when the caller wants none
+    DevBuf<unsigned long long> d_binvalid{bytes};  // rows that failed the check (one word)
+    PinBuf<unsigned long long> h_bwords;           // pinned: the leaf count and the invalid rows
+    // mesh refinement (aq_mesh_refine_batch)
+    DevBuf<Rec> d_rseed{bytes};                    // the failing leaves' children, one segment per depth
+    DevBuf<unsigned> d_rseedrow{bytes};            // ... and their rows
+    DevBuf<unsigned> d_rtab{bytes};                // the depth table (aquad.hip REFINE_TAB_*)
+    PinBuf<unsigned> h_rtab;                       // pinned copy
+    PinBuf<unsigned long long> h_rnodes;           // pinned: the input's node count (one word)
+    DevBuf<double4> d_eparts{bytes};               // aq_mesh_err_batch's block partials (its first call)
+
+    // the leaf buffer of a run that may emit cap_leaves, and its count
+    int ensure_leaves(size_t cap_leaves) {
+        AQ_HIP(d_leaf.grow(cap_leaves));
+        AQ_HIP(d_leafcnt.grow(1));
+        return AQ_OK;
+    }
+    // the sort of nl leaves by l and the scan over `grid` blocks of them; for a batch of `rows` > 0 also the
+    // segmented scan's arrays and, with more than one row, the second pass by row
+    int ensure_sort(size_t nl, size_t sort_bytes, size_t grid, size_t rows = 0) {
+        for (int k = 0; k < 2; ++k) {
+            AQ_HIP(d_mkey[k].grow(nl));
+            AQ_HIP(d_midx[k].grow(nl));
+            if (rows > 1) AQ_HIP(d_bkey[k].grow(nl));
+        }
+        AQ_HIP(d_msort.grow(std::max<size_t>(sort_bytes, 1)));
+        AQ_HIP(d_mparts.grow(grid));
+        if (rows > 0) {
+            AQ_HIP(d_bpflag.grow(grid));
+            AQ_HIP(d_bnode.grow(nl));
+        }
+        return AQ_OK;
+    }
+    // a walk of n rows over a frontier of cap records (own_status: the caller gave no status array; refine: with
+    // refinement's depth table)
+    int ensure_batch(size_t n, size_t cap, size_t cap_leaves, bool own_status, bool refine) {
+        for (int k = 0; k < 2; ++k) AQ_HIP(d_brow[k].grow(cap));
+        if (int rc = ensure_leaves(cap_leaves)) return rc;
+        AQ_HIP(d_binvalid.grow(1));
+        AQ_HIP(d_bfirst.grow(n + 1));
+        if (own_status) AQ_HIP(d_bstatus.grow(n));
+        AQ_HIP(h_bwords.grow(2));
+        if (refine) {
+            AQ_HIP(d_rtab.grow(REFINE_TAB_WORDS));
+            AQ_HIP(h_rtab.grow(REFINE_TAB_WORDS));
+            AQ_HIP(h_rnodes.grow(1));
+        }
+        return AQ_OK;
+    }
+};
+
 }  // namespace
 
 struct aq_ctx {
@@ -270,41 +370,13 @@ struct aq_ctx {
     int gsplit_env = 0;                // AQ_GSPLIT: waves per job of a multi-integral launch (0 = default)
     // level path
     DevBuf<DevResults> d_lres{&dev_bytes};
-    DevBuf<Rec> d_front[2] = {DevBuf<Rec>{&dev_bytes}, DevBuf<Rec>{&dev_bytes}};   // both of one size, or neither
-    DevBuf<unsigned> d_count{&dev_bytes};
-    PinBuf<unsigned> h_fcount;         // aq_frontier_integrate's per-level counts
-    DevBuf<double> d_facc{&dev_bytes}; // aq_frontier_integrate's accumulator (8 doubles, device)
-    PinBuf<double> h_facc;             // pinned copy
+    FrontBufs front{&dev_bytes};       // the frontier pair, its per-depth counts and a walk's accumulator
     DevBuf<LevelPart> d_lparts{&dev_bytes};   // frontier engine: per-block partials of one level step
     bool defer_fold = false;           // aq_level_defer_fold: level steps leave their rows for one later fold
     int level_grid = 0;                // aq_level_step's grid cap (MAXB, or AQ_LEVEL_GRID), set at create
     int lp_pending = 0;                // level-step rows written and not yet folded
     double* lp_acc = nullptr;          // ... into this accumulator (the caller's)
-    // the accepted mesh (aq_integrate_mesh), allocated by its first call and grown on demand
-    DevBuf<Leaf> d_leaf{&dev_bytes};                // leaf records in schedule order
-    DevBuf<unsigned long long> d_leafcnt{&dev_bytes};   // accepted tasks counted by the emitting kernels (one word)
-    DevBuf<double> d_mkey[2] = {DevBuf<double>{&dev_bytes}, DevBuf<double>{&dev_bytes}};       // sort keys in / out
-    DevBuf<unsigned> d_midx[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}}; // leaf indices in / out
-    DevBuf<unsigned char> d_msort{&dev_bytes};      // the sort's scratch
-    DevBuf<double2> d_mparts{&dev_bytes};           // the scan's block partials
-    // the batch of meshes (aq_integrate_mesh_batch), allocated by its first call and grown on demand; it runs in the
-    // frontier buffers and the single mesh's leaf, sort and partial arrays above, and adds:
-    DevBuf<unsigned> d_brow[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}};   // the frontier records' rows
-    DevBuf<unsigned> d_bkey[2] = {DevBuf<unsigned>{&dev_bytes}, DevBuf<unsigned>{&dev_bytes}};   // the second sort's keys in / out
-    DevBuf<unsigned> d_bfirst{&dev_bytes};          // [n + 1] every row's first sorted leaf
-    DevBuf<unsigned> d_bnode{&dev_bytes};           // a sorted leaf's first node | its row's head bit
-    DevBuf<unsigned> d_bpflag{&dev_bytes};          // the segmented scan's "block has a head"
-    DevBuf<unsigned> d_bstatus{&dev_bytes};         // [n] the rows' status when the caller wants none
-    DevBuf<unsigned long long> d_binvalid{&dev_bytes};   // rows that failed the check (one word)
-    PinBuf<unsigned long long> h_bwords;            // pinned: the leaf count and the invalid rows
-    // mesh refinement (aq_mesh_refine_batch), allocated by its first call and grown on demand; it runs in the batch's
-    // buffers above and adds:
-    DevBuf<Rec> d_rseed{&dev_bytes};                // the failing leaves' children, one segment per depth
-    DevBuf<unsigned> d_rseedrow{&dev_bytes};        // ... and their rows
-    DevBuf<unsigned> d_rtab{&dev_bytes};            // the depth table (aquad.hip REFINE_TAB_*)
-    PinBuf<unsigned> h_rtab;                        // pinned copy
-    PinBuf<unsigned long long> h_rnodes;            // pinned: the input's node count (one word)
-    DevBuf<double4> d_eparts{&dev_bytes};           // aq_mesh_err_batch's block partials (its first call)
+    MeshBufs mesh{&dev_bytes};         // the accepted mesh, single, batched and refined (grown by those calls)
     HostBatch batch{&dev_bytes};       // the batch front end's rings and pinned copies (grown by its calls)
     // per-integral parameters (AQ_F_PARAM), allocated by the first parametrised call (ensure_params): NSLOTS + 1
     // rows on the device beside d_bounds, and their pinned staging ring
@@ -916,7 +988,7 @@ static int ctx_init(aq_ctx* c, int device) {
     AQ_HIP(c->h_sync.alloc(1, true, hipHostMallocCoherent | hipHostMallocMapped));
     AQ_HIP(hipHostGetDevicePointer((void**)&c->d_sync, c->h_sync, 0));
     AQ_HIP(c->d_lres.alloc(1, false));
-    AQ_HIP(c->d_count.alloc(AQ_MAX_LEVELS + 2, false));
+    AQ_HIP(c->front.d_count.alloc(AQ_MAX_LEVELS + 2, false));
     AQ_HIP(hipDeviceSynchronize());
     return AQ_OK;
 }
@@ -1365,16 +1437,6 @@ int aq_tasks_per_cu(aq_ctx* ctx, uint64_t* out, int cap) {
     return n;
 }
 
-// The context's two frontier buffers hold at least cap records each. They only grow; a failed
-// allocation leaves neither, so the two always hold the same count and no caller launches on half a pair.
-static int ensure_front(aq_ctx* ctx, size_t cap) {
-    if (ctx->d_front[0].grow(cap) == hipSuccess && ctx->d_front[1].grow(cap) == hipSuccess) return AQ_OK;
-    ctx->d_front[0].reset();
-    ctx->d_front[1].reset();
-    fprintf(stderr, "aquad: no device memory for two frontier buffers of %zu records\n", cap);
-    return AQ_EHIP;
-}
-
 int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64_t* tpl, uint64_t* lpl,
                         int maxlev) {
     if (!ctx) return AQ_EINVAL;
@@ -1383,22 +1445,22 @@ int aq_integrate_levels(aq_ctx* ctx, const aq_problem* p, aq_result* res, uint64
     AQ_HIP(hipSetDevice(ctx->device));
     const int max_depth = p->max_depth ? p->max_depth : AQ_DEFAULT_MAX_DEPTH;
     // 16 M records (512 MiB) per buffer at least, whatever a frontier run left there before
-    if ((rc = ensure_front(ctx, (size_t)1 << 24))) return rc;
-    const size_t front_cap = ctx->d_front[0].count();
+    if ((rc = ctx->front.ensure_front((size_t)1 << 24))) return rc;
+    const size_t front_cap = ctx->front.d_rec[0].count();
     DevResults* dres = ctx->d_lres;
     AQ_HIP(hipMemsetAsync(dres, 0, sizeof(DevResults), ctx->stream));
-    AQ_HIP(hipMemsetAsync(ctx->d_count, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->front.d_count, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
     with_fid(p->integrand, [&](auto F) {
-        hipLaunchKernelGGL((k_root<decltype(F)::value>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->d_front[0],
+        hipLaunchKernelGGL((k_root<decltype(F)::value>), dim3(1), dim3(64), 0, ctx->stream, p->a, p->b, ctx->front.d_rec[0],
                            ctx->d_tab);
     });
     AQ_HIP(hipGetLastError());
     unsigned n = 1;
     int depth = 0;
     for (; n > 0 && depth < AQ_MAX_LEVELS; ++depth) {
-        Rec* in = ctx->d_front[depth & 1];
-        Rec* outb = ctx->d_front[(depth + 1) & 1];
-        unsigned* n_out = ctx->d_count + depth + 1;
+        Rec* in = ctx->front.d_rec[depth & 1];
+        Rec* outb = ctx->front.d_rec[(depth + 1) & 1];
+        unsigned* n_out = ctx->front.d_count + depth + 1;
         const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
         with_fid(p->integrand, [&](auto F) {
             hipLaunchKernelGGL((k_level<decltype(F)::value>), dim3(grid), dim3(256), 0, ctx->stream, in, n, outb, n_out,
@@ -2090,11 +2152,22 @@ static int fold_pending(aq_ctx* ctx) {
     return AQ_OK;
 }
 
+// Which instance of k_level_step a step launches: the plain one, the leaf-emitting one (aq_integrate_mesh) or the
+// batch form (aq_integrate_mesh_batch, aq_mesh_refine_batch), with that instance's trailing argument.
+struct StepSink {
+    enum Kind { NONE, LEAF, BATCH } kind = NONE;
+    BatchSink batch{};   // LEAF: its `leaf` alone
+    StepSink() = default;
+    StepSink(const LeafSink& s) : kind(LEAF) { batch.leaf = s; }
+    StepSink(const BatchSink& s) : kind(BATCH), batch(s) {}
+};
+
 static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint32_t n_in, const uint32_t* d_n_in,
                            double* d_out, uint32_t cap_out, double eps, int depth, int max_depth, uint32_t* d_n_out,
-                           double* d_acc, const LeafSink* sink = nullptr, const BatchSink* bsink = nullptr) {
+                           double* d_acc, const StepSink& sink = {}) {
     if (!ctx || !d_n_out || !d_acc || (n_in && (!d_in || !d_out))) return AQ_EINVAL;
-    if (!integrand_ok(integrand) && !(bsink && integrand == AQ_F_PARAM)) return AQ_EINVAL;
+    // (the batch form alone gathers a theta row per record: AQ_F_PARAM only there)
+    if (!integrand_ok(integrand) && !(sink.kind == StepSink::BATCH && integrand == AQ_F_PARAM)) return AQ_EINVAL;
     if (!(eps >= 0.0) || depth < 0 || max_depth < 1 || max_depth > AQ_MAX_LEVELS - 1) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
     int rc;
@@ -2107,22 +2180,15 @@ static int level_step_impl(aq_ctx* ctx, int integrand, const double* d_in, uint3
     if (ctx->lp_pending && (d_acc != ctx->lp_acc || ctx->lp_pending + grid > LP_CAP) && (rc = fold_pending(ctx)))
         return rc;
     LevelPart* rows = ctx->d_lparts + ctx->lp_pending;
-    if (bsink)   // the batch form (aq_integrate_mesh_batch): every integrand, F_PARAM among them
-        with_stream_fid(integrand, [&](auto F) {
-            hipLaunchKernelGGL((k_level_step<decltype(F)::value, BatchSink>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
-                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
-                               ctx->d_tab, d_n_in, *bsink);
-        });
-    else with_fid(integrand, [&](auto F) {
-        if (sink)   // the leaf-emitting form (aq_integrate_mesh)
-            hipLaunchKernelGGL((k_level_step<decltype(F)::value, LeafSink>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
-                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
-                               ctx->d_tab, d_n_in, *sink);
-        else
-            hipLaunchKernelGGL((k_level_step<decltype(F)::value>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
-                               (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows,
-                               ctx->d_tab, d_n_in);
-    });
+    auto launch = [&](auto F, auto... s) {   // k_level_step<FID> with the sink's instance and trailing argument
+        hipLaunchKernelGGL((k_level_step<decltype(F)::value, decltype(s)...>), dim3(grid), dim3(LEVEL_T), 0, ctx->stream,
+                           (const Rec*)d_in, n_in, (Rec*)d_out, d_n_out, cap_out, eps, depth, max_depth, rows, ctx->d_tab,
+                           d_n_in, s...);
+    };
+    if (sink.kind == StepSink::BATCH)   // every integrand, F_PARAM among them
+        with_stream_fid(integrand, [&](auto F) { launch(F, sink.batch); });
+    else if (sink.kind == StepSink::LEAF) with_fid(integrand, [&](auto F) { launch(F, sink.batch.leaf); });
+    else with_fid(integrand, [&](auto F) { launch(F); });
     AQ_HIP(hipGetLastError());
     ctx->lp_pending += grid;
     ctx->lp_acc = d_acc;
@@ -2177,83 +2243,137 @@ int aq_level_narrow(aq_ctx* ctx, int integrand, double* d_buf0, double* d_buf1, 
                              nullptr);
 }
 
-// aq_frontier_integrate's run; with `sink`, the same run through the leaf-emitting kernels (aq_integrate_mesh).
+// The host side of a frontier walk, which aq_frontier_integrate / aq_integrate_mesh, aq_integrate_mesh_batch and
+// aq_mesh_refine_batch share. The loop itself is aq_frontier_walk.h's, and the callers differ in its four
+// parameters alone (FrontierWalk). A caller runs walk_begin, puts its first records and their count in place (the
+// root and the narrow top; the rows' roots; the retested leaves' children in the seed buffer), then walk_run.
+//
+// walk_begin: the context's frontier buffers for `cap` records a level, the counts and the accumulator zeroed.
+static int walk_begin(aq_ctx* ctx, uint32_t cap) {
+    if (int rc = ctx->front.ensure_walk(cap)) return rc;
+    AQ_HIP(hipMemsetAsync(ctx->front.d_count, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
+    AQ_HIP(hipMemsetAsync(ctx->front.d_acc, 0, sizeof(double) * 8, ctx->stream));
+    return AQ_OK;
+}
+
+// What a walk left, read back and decoded (all zero unless `back`: the one wait behind the walk was reached).
+struct WalkOut {
+    bool back;
+    const unsigned* counts;   // [AQ_MAX_LEVELS + 2] the records of every depth (pinned: until the next walk)
+    double area_hi, area_lo;
+    unsigned long long tasks, leaves;
+    unsigned error;           // ERRB_* bits
+    unsigned levels, widest;  // the deepest level stepped + 1; the widest level's records
+    bool depth_left;          // records left at the depth the walk ended at: AQ_EDEPTH
+};
+
+// Level steps leave their rows for one later fold while this lives; defer_fold is put back on every way out.
+struct DeferFold {
+    aq_ctx* ctx;
+    const bool was;
+    explicit DeferFold(aq_ctx* c) : ctx(c), was(c->defer_fold) { c->defer_fold = true; }
+    ~DeferFold() { ctx->defer_fold = was; }
+};
+
+// walk_run: chained level steps with deferred folds and a host look every w.sync_every levels, one fold of what is
+// pending whether the walk succeeded or not, then the read-backs and ONE wait. `sink` chooses the step's instance;
+// the batch form's rows travel in the mesh group's row arrays beside the frontier buffers. A walk with a seed table
+// (w.seed_end: aq_mesh_refine_batch) appends from the mesh group's seed buffer and reads the depth table back too;
+// the batch form reads the leaf count and the invalid rows back (h_bwords) -- all in front of the one wait.
+static int walk_run(aq_ctx* ctx, const FrontierWalk& w, int integrand, double eps, const StepSink& sink, WalkOut* out) {
+    FrontBufs& fb = ctx->front;
+    MeshBufs& mb = ctx->mesh;
+    unsigned* cnt = fb.d_count;
+    double* acc = fb.d_acc;
+    double* buf[2] = {reinterpret_cast<double*>(fb.d_rec[0].get()), reinterpret_cast<double*>(fb.d_rec[1].get())};
+    unsigned* row[2] = {mb.d_brow[0].get(), mb.d_brow[1].get()};
+    const uint32_t cap = (uint32_t)w.cap;
+    const bool batch = sink.kind == StepSink::BATCH;
+    *out = WalkOut{};
+    DeferFold guard(ctx);
+    const WalkEnd end = frontier_walk(
+        w,   // seed, step, look:
+        [&](int depth, unsigned long long ns) -> int {
+            const unsigned long long at = w.seed_end[depth - 1];
+            hipLaunchKernelGGL(k_mesh_refine_append, dim3((unsigned)((ns + REFINE_APPEND - 1) / REFINE_APPEND)), dim3(256), 0,
+                               ctx->stream, (const Rec*)(mb.d_rseed.get() + at), (const unsigned*)(mb.d_rseedrow.get() + at),
+                               (unsigned)ns, (Rec*)buf[depth & 1], row[depth & 1], cnt + depth, cap,
+                               mb.d_rtab.get() + REFINE_TAB_ERR);
+            AQ_HIP(hipGetLastError());
+            return AQ_OK;
+        },
+        [&](int depth, unsigned long long n_in) -> int {
+            StepSink s = sink;
+            if (batch) s.batch.row_in = row[depth & 1], s.batch.row_out = row[(depth + 1) & 1];
+            return level_step_impl(ctx, integrand, buf[depth & 1], (uint32_t)n_in, cnt + depth, buf[(depth + 1) & 1], cap, eps,
+                                   depth, w.max_depth, cnt + depth + 1, acc, s);
+        },
+        [&](int depth, unsigned long long* now) -> int {
+            if (int rc = fold_pending(ctx)) return rc;
+            AQ_HIP(hipMemcpyAsync(fb.h_count, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+            AQ_HIP(hipStreamSynchronize(ctx->stream));
+            *now = fb.h_count[0];
+            return AQ_OK;
+        });
+    int rc = end.rc;
+    if (rc == AQ_OK) rc = fold_pending(ctx);
+    else (void)fold_pending(ctx);
+    AQ_HIP(hipMemcpyAsync(fb.h_count, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(fb.h_acc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (batch) {
+        AQ_HIP(hipMemcpyAsync(mb.h_bwords, mb.d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        AQ_HIP(hipMemcpyAsync(mb.h_bwords + 1, mb.d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              ctx->stream));
+    }
+    if (w.seed_end)
+        AQ_HIP(hipMemcpyAsync(mb.h_rtab, mb.d_rtab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    const double* a = fb.h_acc;
+    const unsigned* c = fb.h_count;
+    *out = WalkOut{true, c, a[0], a[1], (unsigned long long)a[2], (unsigned long long)a[3], (unsigned)a[4], (unsigned)a[5],
+                   *std::max_element(c, c + AQ_MAX_LEVELS + 2), !w.empty() && c[std::min(end.depth, AQ_MAX_LEVELS + 1)] > 0};
+    return rc;
+}
+
+// aq_frontier_integrate's run: the frontier engine of ppls_amd/frontier.py for ONE GPU with its host loop in C --
+// the root, the narrow top in one launch (<= 2^12 records a level), then the walk from there (the Python loop's
+// per-level torch / ctypes work, several us a level, is what this saves). With `sink`, the same run through the
+// leaf-emitting kernels (aq_integrate_mesh).
 static int frontier_run(aq_ctx* ctx, const aq_problem* p, uint32_t cap, int sync_every, aq_result* res,
                         uint64_t* tpl, uint64_t* lpl, int maxlev, const LeafSink* sink) {
-    // The frontier engine of ppls_amd/frontier.py for ONE GPU with its host loop in C: the root, the
-    // narrow top in one launch, then chained level steps (device counts, deferred folds) with a host
-    // look at the frontier size every sync_every levels -- the Python loop's per-level torch / ctypes
-    // work (several us a level) is what this saves.
     if (!ctx || cap < 2 || sync_every < 1 || maxlev < 0) return AQ_EINVAL;
     int rc = validate(p);
     if (rc) return rc;
     AQ_HIP(hipSetDevice(ctx->device));
     const int max_depth = p->max_depth ? p->max_depth : AQ_DEFAULT_MAX_DEPTH;
-    if ((rc = ensure_front(ctx, cap))) return rc;
-    AQ_HIP(ctx->d_facc.grow(8));
-    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
-    AQ_HIP(ctx->h_facc.grow(8));
-    unsigned* cnt = ctx->d_count;
-    double* acc = ctx->d_facc;
-    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
-    AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
-    AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
+    if ((rc = walk_begin(ctx, cap))) return rc;
+    unsigned* cnt = ctx->front.d_count;
+    double* buf[2] = {reinterpret_cast<double*>(ctx->front.d_rec[0].get()),
+                      reinterpret_cast<double*>(ctx->front.d_rec[1].get())};
     AQ_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cnt), 1, 1, ctx->stream));   // counts[0] = the root
     if ((rc = aq_frontier_root(ctx, p->integrand, p->a, p->b, buf[0]))) return rc;
-    const bool defer0 = ctx->defer_fold;
-    ctx->defer_fold = true;
-    int depth = std::min(13, max_depth - 1);   // the narrow top (<= 2^12 records a level): one launch
-    if (depth > 0 &&
-        (rc = level_narrow_impl(ctx, p->integrand, buf[0], buf[1], cap, cnt, 0, depth, p->eps, max_depth, acc, sink))) {
-        ctx->defer_fold = defer0;
+    const int top = std::max(std::min(13, max_depth - 1), 0);   // the narrow top: one launch
+    if (top > 0 && (rc = level_narrow_impl(ctx, p->integrand, buf[0], buf[1], cap, cnt, 0, top, p->eps, max_depth,
+                                           ctx->front.d_acc, sink)))
         return rc;
-    }
-    depth = std::max(depth, 0);
-    unsigned long long bound = std::min<unsigned long long>(1ull << depth, cap);
-    unsigned n = 1;
-    int since = 0;
-    while (depth <= max_depth && depth < AQ_MAX_LEVELS) {
-        rc = level_step_impl(ctx, p->integrand, buf[depth & 1], (uint32_t)bound, cnt + depth, buf[(depth + 1) & 1], cap,
-                             p->eps, depth, max_depth, cnt + depth + 1, acc, sink);
-        if (rc) break;
-        ++depth;
-        bound = std::min<unsigned long long>(2 * bound, cap);
-        if (++since == sync_every) {
-            since = 0;
-            if ((rc = fold_pending(ctx))) break;
-            AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-            AQ_HIP(hipStreamSynchronize(ctx->stream));
-            n = ctx->h_fcount[0];
-            if (n == 0) break;
-            if (n > cap) { rc = AQ_EOVERFLOW; break; }
-            bound = n;
-        }
-    }
-    ctx->defer_fold = defer0;
-    if (rc == AQ_OK) rc = fold_pending(ctx);
-    else (void)fold_pending(ctx);
-    AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_facc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (rc) return rc;
-    const double* a = ctx->h_facc;
-    const unsigned* c = ctx->h_fcount;
+    const FrontierWalk w{top, std::min<unsigned long long>(1ull << top, cap), cap, max_depth, sync_every};
+    WalkOut o;
+    if ((rc = walk_run(ctx, w, p->integrand, p->eps, sink ? StepSink(*sink) : StepSink(), &o))) return rc;
     HostOut& h = ctx->last;
     h = HostOut();
-    h.area = a[0] + a[1];
-    h.tasks = (unsigned long long)a[2];
-    h.leaves = (unsigned long long)a[3];
-    h.error = (unsigned)a[4];
-    h.levels = (unsigned)a[5];
-    for (int d = 0; d < AQ_MAX_LEVELS && d + 1 < AQ_MAX_LEVELS + 2; ++d) {
-        h.hist[d] = c[d];
-        h.hist[AQ_MAX_LEVELS + d] = c[d] - c[d + 1] / 2u;
+    h.area = o.area_hi + o.area_lo;
+    h.tasks = o.tasks;
+    h.leaves = o.leaves;
+    h.error = o.error;
+    h.levels = o.levels;
+    for (int d = 0; d < AQ_MAX_LEVELS; ++d) {
+        h.hist[d] = o.counts[d];
+        h.hist[AQ_MAX_LEVELS + d] = o.counts[d] - o.counts[d + 1] / 2u;
     }
     ctx->last_valid = true;
     fill_result(ctx, h, res);
-    rc = err_from_bits(h.error);
-    if (rc) return rc;
-    if (c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
+    if ((rc = err_from_bits(h.error))) return rc;
+    if (o.depth_left) return AQ_EDEPTH;
     return aq_level_histogram(ctx, tpl, lpl, maxlev);
 }
 
@@ -2275,10 +2395,10 @@ int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, i
     *n_nodes = 0;
     AQ_HIP(hipSetDevice(ctx->device));
     const size_t cap_leaves = (size_t)((cap_nodes - 1) / 2);
-    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
-    AQ_HIP(ctx->d_leafcnt.grow(1));
-    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
-    const LeafSink sink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves};
+    MeshBufs& mb = ctx->mesh;
+    if ((rc = mb.ensure_leaves(cap_leaves))) return rc;
+    AQ_HIP(hipMemsetAsync(mb.d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    const LeafSink sink{mb.d_leaf, mb.d_leafcnt, (unsigned long long)cap_leaves};
     aq_result local{};
     aq_result* r = res ? res : &local;
     if ((rc = frontier_run(ctx, p, frontier_cap, sync_every, r, nullptr, nullptr, 0, &sink))) return rc;
@@ -2290,22 +2410,16 @@ int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, i
     hipError_t he = hipSuccess;
     const size_t sort_bytes = mesh_sort_scratch_bytes(n, &he);
     AQ_HIP(he);
-    for (int k = 0; k < 2; ++k) {
-        AQ_HIP(ctx->d_mkey[k].grow(n));
-        AQ_HIP(ctx->d_midx[k].grow(n));
-    }
-    AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
-    AQ_HIP(ctx->d_mparts.grow(grid));
-    hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), n,
-                       ctx->d_mkey[0].get(), ctx->d_midx[0].get());
+    if ((rc = mb.ensure_sort(n, sort_bytes, grid))) return rc;
+    hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, mb.d_leaf.get(), n, mb.d_mkey[0].get(),
+                       mb.d_midx[0].get());
     AQ_HIP(hipGetLastError());
-    AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], n,
-                     ctx->stream));
+    AQ_HIP(mesh_sort(mb.d_msort, sort_bytes, mb.d_mkey[0], mb.d_mkey[1], mb.d_midx[0], mb.d_midx[1], n, ctx->stream));
     // node pairs go out as one 16-byte store where the caller's arrays allow
     const bool vec = (((uintptr_t)io->x | (uintptr_t)io->f | (uintptr_t)io->cum) & 15u) == 0;
-    const Leaf* lv = ctx->d_leaf;
-    const unsigned* idx = ctx->d_midx[1];
-    double2* parts = ctx->d_mparts;
+    const Leaf* lv = mb.d_leaf;
+    const unsigned* idx = mb.d_midx[1];
+    double2* parts = mb.d_mparts;
     if (vec)
         hipLaunchKernelGGL(k_mesh_expand<true>, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, n, io->x, io->f,
                            io->cum, io->level, parts);
@@ -2327,6 +2441,7 @@ int aq_integrate_mesh(aq_ctx* ctx, const aq_problem* p, uint32_t frontier_cap, i
 // The back half of aq_integrate_mesh_batch, which aq_mesh_refine_batch shares: the nl leaves of n rows in the context's
 // leaf buffer, in any order, sorted by (row, l) and laid out row after row (aquad.hip k_mesh_batch_*). Waits.
 static int mesh_batch_back(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, unsigned nl) {
+    MeshBufs& mb = ctx->mesh;
     const unsigned nr = (unsigned)n;
     const unsigned grid = (nl + MESH_T - 1) / MESH_T, rgrid = (nr + 1 + MESH_T - 1) / MESH_T;
     unsigned bits = 0;
@@ -2340,48 +2455,40 @@ static int mesh_batch_back(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, un
             sort_bytes = std::max(sort_bytes, mesh_sort_rows_scratch_bytes(nl, bits, &he));
             AQ_HIP(he);
         }
-        for (int k = 0; k < 2; ++k) {
-            AQ_HIP(ctx->d_mkey[k].grow(nl));
-            AQ_HIP(ctx->d_midx[k].grow(nl));
-            if (n > 1) AQ_HIP(ctx->d_bkey[k].grow(nl));
-        }
-        AQ_HIP(ctx->d_msort.grow(std::max<size_t>(sort_bytes, 1)));
-        AQ_HIP(ctx->d_mparts.grow(grid));
-        AQ_HIP(ctx->d_bpflag.grow(grid));
-        AQ_HIP(ctx->d_bnode.grow(nl));
-        hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), nl,
-                           ctx->d_mkey[0].get(), ctx->d_midx[0].get());
+        if (int rc = mb.ensure_sort(nl, sort_bytes, grid, n)) return rc;
+        hipLaunchKernelGGL(k_mesh_keys, dim3(grid), dim3(MESH_T), 0, ctx->stream, mb.d_leaf.get(), nl,
+                           mb.d_mkey[0].get(), mb.d_midx[0].get());
         AQ_HIP(hipGetLastError());
-        AQ_HIP(mesh_sort(ctx->d_msort, sort_bytes, ctx->d_mkey[0], ctx->d_mkey[1], ctx->d_midx[0], ctx->d_midx[1], nl,
+        AQ_HIP(mesh_sort(mb.d_msort, sort_bytes, mb.d_mkey[0], mb.d_mkey[1], mb.d_midx[0], mb.d_midx[1], nl,
                          ctx->stream));
-        idx = ctx->d_midx[1];
+        idx = mb.d_midx[1];
         if (n > 1) {   // the second, stable pass: by row
-            hipLaunchKernelGGL(k_mesh_batch_rowkeys, dim3(grid), dim3(MESH_T), 0, ctx->stream, ctx->d_leaf.get(), idx, nl,
-                               ctx->d_bkey[0].get());
+            hipLaunchKernelGGL(k_mesh_batch_rowkeys, dim3(grid), dim3(MESH_T), 0, ctx->stream, mb.d_leaf.get(), idx, nl,
+                               mb.d_bkey[0].get());
             AQ_HIP(hipGetLastError());
-            AQ_HIP(mesh_sort_rows(ctx->d_msort, sort_bytes, ctx->d_bkey[0], ctx->d_bkey[1], ctx->d_midx[1], ctx->d_midx[0],
+            AQ_HIP(mesh_sort_rows(mb.d_msort, sort_bytes, mb.d_bkey[0], mb.d_bkey[1], mb.d_midx[1], mb.d_midx[0],
                                   nl, bits, ctx->stream));
-            idx = ctx->d_midx[0];
+            idx = mb.d_midx[0];
         }
     }
-    const Leaf* lv = ctx->d_leaf;
-    unsigned* first = ctx->d_bfirst;
+    const Leaf* lv = mb.d_leaf;
+    unsigned* first = mb.d_bfirst;
     hipLaunchKernelGGL(k_mesh_batch_first, dim3(rgrid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl, nr, first);
     AQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_mesh_batch_offsets, dim3(1), dim3(MESH_T), 0, ctx->stream, (const unsigned*)first, nr,
                        (unsigned long long*)io->offsets);
     AQ_HIP(hipGetLastError());
     if (nl > 0) {
-        double2* parts = ctx->d_mparts;
+        double2* parts = mb.d_mparts;
         hipLaunchKernelGGL(k_mesh_batch_expand, dim3(grid), dim3(MESH_T), 0, ctx->stream, lv, idx, nl,
                            (const unsigned*)first, (const unsigned long long*)io->offsets, io->x, io->f, io->cum,
-                           io->level, ctx->d_bnode.get(), parts, ctx->d_bpflag.get());
+                           io->level, mb.d_bnode.get(), parts, mb.d_bpflag.get());
         AQ_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_mesh_batch_scan_parts, dim3(1), dim3(MESH_T), 0, ctx->stream, parts,
-                           (const unsigned*)ctx->d_bpflag.get(), grid);
+                           (const unsigned*)mb.d_bpflag.get(), grid);
         AQ_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_mesh_batch_cum, dim3(grid), dim3(MESH_T), 0, ctx->stream, nl,
-                           (const unsigned*)ctx->d_bnode.get(), io->cum, (const double2*)parts);
+                           (const unsigned*)mb.d_bnode.get(), io->cum, (const double2*)parts);
         AQ_HIP(hipGetLastError());
     }
     if (io->area || io->accepted || io->tasks) {
@@ -2394,8 +2501,8 @@ static int mesh_batch_back(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, un
     return AQ_OK;
 }
 
-// Many meshes per call: frontier_run's loop over ONE frontier that holds every row's records of a depth (level 0:
-// the valid rows' roots, compacted by k_mesh_batch_roots; no narrow top -- level 0 is already n records wide, and a
+// Many meshes per call: frontier_run's walk over ONE frontier that holds every row's records of a depth, from depth 0
+// (the valid rows' roots, compacted by k_mesh_batch_roots; no narrow top -- level 0 is already n records wide, and a
 // small batch's few narrow levels cost a launch each as a lone mesh's levels past the top do), then the leaves
 // ordered by (row, l) and laid out row after row (aquad.hip k_mesh_batch_*). Blocks, as aq_integrate_mesh does.
 int aq_integrate_mesh_batch(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, double eps, int integrand,
@@ -2412,76 +2519,33 @@ int aq_integrate_mesh_batch(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, d
     const uint32_t cap = frontier_cap;
     const unsigned nr = (unsigned)n;   // n <= frontier_cap < 2^32
     const size_t cap_leaves = (size_t)(cap_nodes / 2);   // a mesh that fits has at most (cap_nodes - 1) / 2 leaves
+    MeshBufs& mb = ctx->mesh;
     int rc;
-    if ((rc = ensure_front(ctx, cap))) return rc;
-    for (int k = 0; k < 2; ++k) AQ_HIP(ctx->d_brow[k].grow(cap));
-    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
-    AQ_HIP(ctx->d_leafcnt.grow(1));
-    AQ_HIP(ctx->d_binvalid.grow(1));
-    AQ_HIP(ctx->d_bfirst.grow(n + 1));
-    if (!io->status) AQ_HIP(ctx->d_bstatus.grow(n));
-    AQ_HIP(ctx->d_facc.grow(8));
-    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
-    AQ_HIP(ctx->h_facc.grow(8));
-    AQ_HIP(ctx->h_bwords.grow(2));
-    unsigned* cnt = ctx->d_count;
-    double* acc = ctx->d_facc;
-    unsigned* status = io->status ? io->status : ctx->d_bstatus.get();
-    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
-    unsigned* row[2] = {ctx->d_brow[0].get(), ctx->d_brow[1].get()};
-    AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
-    AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
-    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
-    AQ_HIP(hipMemsetAsync(ctx->d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
+    if ((rc = mb.ensure_batch(n, cap, cap_leaves, !io->status, false))) return rc;
+    if ((rc = walk_begin(ctx, cap))) return rc;
+    unsigned* status = io->status ? io->status : mb.d_bstatus.get();
+    AQ_HIP(hipMemsetAsync(mb.d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(mb.d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
     with_stream_fid(integrand, [&](auto F) {
         hipLaunchKernelGGL((k_mesh_batch_roots<decltype(F)::value>), dim3((nr + 255u) / 256u), dim3(256), 0, ctx->stream,
-                           io->a, io->b, io->theta, nr, (Rec*)buf[0], row[0], cnt, status, ctx->d_binvalid.get(),
-                           ctx->d_tab);
+                           io->a, io->b, io->theta, nr, ctx->front.d_rec[0].get(), mb.d_brow[0].get(),
+                           ctx->front.d_count.get(), status, mb.d_binvalid.get(), ctx->d_tab);
     });
     AQ_HIP(hipGetLastError());
-    const bool defer0 = ctx->defer_fold;
-    ctx->defer_fold = true;
-    int depth = 0, since = 0;
-    unsigned long long bound = nr;   // level 0 holds at most n records; a level at most twice the one before
-    while (depth <= max_depth && depth < AQ_MAX_LEVELS) {
-        const BatchSink sink{LeafSink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves}, row[depth & 1],
-                             row[(depth + 1) & 1], io->theta, status, nr};
-        rc = level_step_impl(ctx, integrand, buf[depth & 1], (uint32_t)bound, cnt + depth, buf[(depth + 1) & 1], cap, eps,
-                             depth, max_depth, cnt + depth + 1, acc, nullptr, &sink);
-        if (rc) break;
-        ++depth;
-        bound = std::min<unsigned long long>(2 * bound, cap);
-        if (++since == sync_every) {
-            since = 0;
-            if ((rc = fold_pending(ctx))) break;
-            AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-            AQ_HIP(hipStreamSynchronize(ctx->stream));
-            const unsigned now = ctx->h_fcount[0];
-            if (now == 0) break;
-            if (now > cap) { rc = AQ_EOVERFLOW; break; }
-            bound = now;
-        }
-    }
-    ctx->defer_fold = defer0;
-    if (rc == AQ_OK) rc = fold_pending(ctx);
-    else (void)fold_pending(ctx);
-    AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_facc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_bwords, ctx->d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_bwords + 1, ctx->d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    AQ_HIP(hipStreamSynchronize(ctx->stream));
-    info->invalid_rows = ctx->h_bwords[1];
+    const FrontierWalk w{0, nr, cap, max_depth, sync_every};   // from depth 0, which holds at most n records
+    const BatchSink sink{LeafSink{mb.d_leaf, mb.d_leafcnt, (unsigned long long)cap_leaves}, nullptr, nullptr, io->theta,
+                         status, nr};   // (the rows' arrays of a depth: walk_run's)
+    WalkOut o;
+    rc = walk_run(ctx, w, integrand, eps, sink, &o);
+    if (o.back) info->invalid_rows = mb.h_bwords[1];
     if (rc) return rc;
-    const double* a = ctx->h_facc;
-    const unsigned* c = ctx->h_fcount;
-    if ((rc = err_from_bits((unsigned)a[4]))) return rc;   // a level past frontier_cap, or a refine at max_depth
-    if (c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
-    const uint64_t leaves = ctx->h_bwords[0];   // every accepted task emitted (or, past the capacity, counted) one leaf
+    if ((rc = err_from_bits(o.error))) return rc;   // a level past frontier_cap, or a refine at max_depth
+    if (o.depth_left) return AQ_EDEPTH;
+    const uint64_t leaves = mb.h_bwords[0];   // every accepted task emitted (or, past the capacity, counted) one leaf
     info->leaves = leaves;
-    info->tasks = (uint64_t)a[2];
-    info->levels = (uint32_t)a[5];
-    for (int d = 0; d < AQ_MAX_LEVELS + 2; ++d) info->widest_level = std::max(info->widest_level, (uint32_t)c[d]);
+    info->tasks = o.tasks;
+    info->levels = o.levels;
+    info->widest_level = o.widest;
     info->n_nodes = 2 * leaves + (n - info->invalid_rows);
     if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
     return mesh_batch_back(ctx, n, io, (unsigned)leaves);
@@ -2490,8 +2554,9 @@ int aq_integrate_mesh_batch(aq_ctx* ctx, size_t n, const aq_mesh_batch_io* io, d
 // A batch mesh continued to a smaller eps: aq_integrate_mesh_batch with its roots kernel replaced by the retest of
 // the input's leaves (aquad.hip k_mesh_refine_*). The survivors go straight to the leaf buffer; the failing leaves'
 // children wait in the seed buffer, one segment per depth, and join the frontier of their depth just before that
-// depth's step. The loop starts at the first depth that has seeds and ends at an empty level only when no deeper
-// segment is left. Two host looks before the loop: the input's node count, then the per-depth counts.
+// depth's step. The walk starts at the first depth that has seeds and ends at an empty level only when no deeper
+// segment is left (aq_frontier_walk.h). Two host looks before the walk: the input's node count, then the per-depth
+// counts.
 int aq_mesh_refine_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
                          const uint8_t* d_level, const double* d_theta, const uint8_t* d_active, double eps, int integrand,
                          const aq_mesh_batch_io* out, uint32_t frontier_cap, int sync_every, uint64_t cap_nodes,
@@ -2509,129 +2574,68 @@ int aq_mesh_refine_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const
     const uint32_t cap = frontier_cap;
     const unsigned nr = (unsigned)n;
     const size_t cap_leaves = (size_t)(cap_nodes / 2);
+    MeshBufs& mb = ctx->mesh;
     int rc;
-    if ((rc = ensure_front(ctx, cap))) return rc;
-    for (int k = 0; k < 2; ++k) AQ_HIP(ctx->d_brow[k].grow(cap));
-    AQ_HIP(ctx->d_leaf.grow(cap_leaves));
-    AQ_HIP(ctx->d_leafcnt.grow(1));
-    AQ_HIP(ctx->d_binvalid.grow(1));
-    AQ_HIP(ctx->d_bfirst.grow(n + 1));
-    if (!out->status) AQ_HIP(ctx->d_bstatus.grow(n));
-    AQ_HIP(ctx->d_facc.grow(8));
-    AQ_HIP(ctx->h_fcount.grow(AQ_MAX_LEVELS + 2));
-    AQ_HIP(ctx->h_facc.grow(8));
-    AQ_HIP(ctx->h_bwords.grow(2));
-    AQ_HIP(ctx->d_rtab.grow(REFINE_TAB_WORDS));
-    AQ_HIP(ctx->h_rtab.grow(REFINE_TAB_WORDS));
-    AQ_HIP(ctx->h_rnodes.grow(1));
-    unsigned* cnt = ctx->d_count;
-    double* acc = ctx->d_facc;
-    unsigned* tab = ctx->d_rtab;
-    unsigned* status = out->status ? out->status : ctx->d_bstatus.get();
-    double* buf[2] = {reinterpret_cast<double*>(ctx->d_front[0].get()), reinterpret_cast<double*>(ctx->d_front[1].get())};
-    unsigned* row[2] = {ctx->d_brow[0].get(), ctx->d_brow[1].get()};
-    AQ_HIP(hipMemcpyAsync(ctx->h_rnodes, d_offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), ctx->stream));
-    AQ_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 8, ctx->stream));
+    if ((rc = mb.ensure_batch(n, cap, cap_leaves, !out->status, true))) return rc;
+    unsigned* tab = mb.d_rtab;
+    unsigned* status = out->status ? out->status : mb.d_bstatus.get();
+    AQ_HIP(hipMemcpyAsync(mb.h_rnodes, d_offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = walk_begin(ctx, cap))) return rc;
     AQ_HIP(hipMemsetAsync(tab, 0, sizeof(unsigned) * REFINE_TAB_WORDS, ctx->stream));
-    AQ_HIP(hipMemsetAsync(ctx->d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
-    AQ_HIP(hipMemsetAsync(ctx->d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(mb.d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(mb.d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_mesh_refine_rows, dim3((nr + REFINE_T - 1) / REFINE_T), dim3(REFINE_T), 0, ctx->stream,
-                       (const unsigned long long*)d_offsets, nr, status, ctx->d_binvalid.get());
+                       (const unsigned long long*)d_offsets, nr, status, mb.d_binvalid.get());
     AQ_HIP(hipGetLastError());
     AQ_HIP(hipStreamSynchronize(ctx->stream));   // the first look: the input's nodes
-    const unsigned long long m_in = ctx->h_rnodes[0];
+    const unsigned long long m_in = mb.h_rnodes[0];
     if (m_in > (1ull << 31)) return AQ_EINVAL;
     const RefineIn in{(const unsigned long long*)d_offsets, d_x, d_f, d_level, d_active, nr, m_in, eps, max_depth};
     const unsigned cgrid = (unsigned)((m_in + REFINE_T - 1) / REFINE_T);
-    const LeafSink lsink{ctx->d_leaf, ctx->d_leafcnt, (unsigned long long)cap_leaves};
+    const LeafSink lsink{mb.d_leaf, mb.d_leafcnt, (unsigned long long)cap_leaves};
     if (cgrid) {
         hipLaunchKernelGGL(k_mesh_refine_classify, dim3(cgrid), dim3(REFINE_T), 0, ctx->stream, in, lsink, status, tab);
         AQ_HIP(hipGetLastError());
     }
-    AQ_HIP(hipMemcpyAsync(ctx->h_rtab, tab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(mb.h_rtab, tab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
     AQ_HIP(hipStreamSynchronize(ctx->stream));   // the second look: the failing leaves by depth
     unsigned long long seg[AQ_MAX_LEVELS + 1];   // the seed records of depth e are [seg[e - 1], seg[e])
     int first_depth = -1, last_depth = -1;       // the first and the last depth that has seeds
     unsigned long long pre = 0;
     for (int d = 0; d < AQ_MAX_LEVELS; ++d) {    // the children of the failing leaves of depth d: depth d + 1
         seg[d] = 2 * pre;
-        if (ctx->h_rtab[d]) {
+        if (mb.h_rtab[d]) {
             if (first_depth < 0) first_depth = d + 1;
             last_depth = d + 1;
         }
-        pre += ctx->h_rtab[d];
+        pre += mb.h_rtab[d];
     }
     seg[AQ_MAX_LEVELS] = 2 * pre;
     const unsigned long long n_seed = 2 * pre;   // <= the input's nodes <= 2^31
-    const unsigned deep_fail = ctx->h_rtab[REFINE_TAB_DEPTHFAIL];
+    const unsigned deep_fail = mb.h_rtab[REFINE_TAB_DEPTHFAIL];
     info->reseeded = pre + deep_fail;
-    auto seeds_of = [&](int depth) -> unsigned long long {   // records that join the frontier of `depth`
-        return depth >= 1 && depth <= AQ_MAX_LEVELS ? seg[depth] - seg[depth - 1] : 0ull;
-    };
     if (n_seed) {
-        AQ_HIP(ctx->d_rseed.grow(n_seed));
-        AQ_HIP(ctx->d_rseedrow.grow(n_seed));
-        hipLaunchKernelGGL(k_mesh_refine_seed, dim3(cgrid), dim3(REFINE_T), 0, ctx->stream, in, tab, ctx->d_rseed.get(),
-                           ctx->d_rseedrow.get(), n_seed);
+        AQ_HIP(mb.d_rseed.grow(n_seed));
+        AQ_HIP(mb.d_rseedrow.grow(n_seed));
+        hipLaunchKernelGGL(k_mesh_refine_seed, dim3(cgrid), dim3(REFINE_T), 0, ctx->stream, in, tab, mb.d_rseed.get(),
+                           mb.d_rseedrow.get(), n_seed);
         AQ_HIP(hipGetLastError());
     }
-    const bool defer0 = ctx->defer_fold;
-    ctx->defer_fold = true;
-    int depth = first_depth < 0 ? 0 : first_depth, since = 0;
-    unsigned long long bound = 0;   // the children the step before may have appended
-    rc = AQ_OK;
-    while (first_depth >= 0 && depth <= max_depth && depth < AQ_MAX_LEVELS) {
-        const unsigned long long ns = seeds_of(depth);
-        if (ns) {
-            hipLaunchKernelGGL(k_mesh_refine_append, dim3((unsigned)((ns + REFINE_APPEND - 1) / REFINE_APPEND)), dim3(256), 0,
-                               ctx->stream, (const Rec*)(ctx->d_rseed.get() + seg[depth - 1]),
-                               (const unsigned*)(ctx->d_rseedrow.get() + seg[depth - 1]), (unsigned)ns,
-                               (Rec*)buf[depth & 1], row[depth & 1], cnt + depth, cap, tab + REFINE_TAB_ERR);
-            if (hipGetLastError() != hipSuccess) { rc = AQ_EHIP; break; }   // (leaves the loop: defer_fold is put back)
-        }
-        const unsigned long long n_in = std::min<unsigned long long>(bound + ns, cap);
-        const BatchSink sink{lsink, row[depth & 1], row[(depth + 1) & 1], d_theta, status, nr};
-        rc = level_step_impl(ctx, integrand, buf[depth & 1], (uint32_t)n_in, cnt + depth, buf[(depth + 1) & 1], cap, eps,
-                             depth, max_depth, cnt + depth + 1, acc, nullptr, &sink);
-        if (rc) break;
-        ++depth;
-        bound = std::min<unsigned long long>(2 * n_in, cap);
-        if (bound == 0 && depth > last_depth) break;   // nothing can be left (known without a look)
-        if (++since == sync_every) {
-            since = 0;
-            if ((rc = fold_pending(ctx))) break;
-            AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt + depth, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-            AQ_HIP(hipStreamSynchronize(ctx->stream));
-            const unsigned now = ctx->h_fcount[0];
-            if (now == 0 && depth > last_depth) break;
-            if (now > cap) { rc = AQ_EOVERFLOW; break; }
-            bound = now;
-        }
-    }
-    ctx->defer_fold = defer0;
-    if (rc == AQ_OK) rc = fold_pending(ctx);
-    else (void)fold_pending(ctx);
-    AQ_HIP(hipMemcpyAsync(ctx->h_fcount, cnt, sizeof(unsigned) * (AQ_MAX_LEVELS + 2), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_facc, acc, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_bwords, ctx->d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_bwords + 1, ctx->d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    AQ_HIP(hipMemcpyAsync(ctx->h_rtab, tab, sizeof(unsigned) * REFINE_TAB_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    AQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (rc) return rc;
-    const double* a = ctx->h_facc;
-    const unsigned* c = ctx->h_fcount;
-    info->evaluated = (uint64_t)a[2];
+    // from the first depth that has seeds, empty until they join; nothing to walk without any
+    const FrontierWalk w{std::max(first_depth, 0), 0, cap, max_depth, sync_every, seg, last_depth};
+    const BatchSink sink{lsink, nullptr, nullptr, d_theta, status, nr};   // (the rows' arrays of a depth: walk_run's)
+    WalkOut o;
+    if ((rc = walk_run(ctx, w, integrand, eps, sink, &o))) return rc;
+    info->evaluated = o.tasks;
     // a level past frontier_cap (a step's children, or the seeds behind them), or a refine at max_depth (a failing
     // input leaf, or a later task)
-    if ((rc = err_from_bits((unsigned)a[4] | ctx->h_rtab[REFINE_TAB_ERR] | (deep_fail ? (unsigned)ERRB_DEPTH : 0u)))) return rc;
-    if (first_depth >= 0 && c[std::min(depth, AQ_MAX_LEVELS + 1)] > 0) return AQ_EDEPTH;
-    const uint64_t leaves = ctx->h_bwords[0], with_nodes = n - ctx->h_bwords[1];
+    if ((rc = err_from_bits(o.error | mb.h_rtab[REFINE_TAB_ERR] | (deep_fail ? (unsigned)ERRB_DEPTH : 0u)))) return rc;
+    if (o.depth_left) return AQ_EDEPTH;
+    const uint64_t leaves = mb.h_bwords[0], with_nodes = n - mb.h_bwords[1];
     info->leaves = leaves;
     info->tasks = 2 * leaves - with_nodes;
-    info->levels = std::max((uint32_t)a[5], (uint32_t)ctx->h_rtab[REFINE_TAB_LEVELS]);
-    for (int d = 0; d < AQ_MAX_LEVELS + 2; ++d) info->widest_level = std::max(info->widest_level, (uint32_t)c[d]);
+    info->levels = std::max((uint32_t)o.levels, (uint32_t)mb.h_rtab[REFINE_TAB_LEVELS]);
+    info->widest_level = o.widest;
     info->n_nodes = 2 * leaves + with_nodes;
     if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
     return mesh_batch_back(ctx, n, out, (unsigned)leaves);
@@ -2645,12 +2649,12 @@ int aq_mesh_err_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const do
     if (n == 0 || (!d_err_abs && !d_err_signed)) return AQ_OK;
     if (n > 0x7fffffffull / MESH_ERR_B) return AQ_EINVAL;
     AQ_HIP(hipSetDevice(ctx->device));
-    AQ_HIP(ctx->d_eparts.grow(n * MESH_ERR_B));
+    AQ_HIP(ctx->mesh.d_eparts.grow(n * MESH_ERR_B));
     hipLaunchKernelGGL(k_mesh_err_parts, dim3((unsigned)(n * MESH_ERR_B)), dim3(MESH_T), 0, ctx->stream,
-                       (const unsigned long long*)d_offsets, d_x, d_f, ctx->d_eparts.get());
+                       (const unsigned long long*)d_offsets, d_x, d_f, ctx->mesh.d_eparts.get());
     AQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_mesh_err_finish, dim3((unsigned)((n + MESH_T - 1) / MESH_T)), dim3(MESH_T), 0, ctx->stream,
-                       (const unsigned long long*)d_offsets, (unsigned)n, (const double4*)ctx->d_eparts.get(), d_err_abs,
+                       (const unsigned long long*)d_offsets, (unsigned)n, (const double4*)ctx->mesh.d_eparts.get(), d_err_abs,
                        d_err_signed);
     AQ_HIP(hipGetLastError());
     return AQ_OK;

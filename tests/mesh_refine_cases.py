@@ -294,6 +294,79 @@ def test_rows_without_nodes_and_device_memory(torch):
         assert np.all(run.accepted == 0) and np.all(run.tasks == 0) and np.all(run.x == POISON)
 
 
+def test_walks_interleaved_on_one_context(torch):
+    """The frontier walk's callers in turn on ONE context -- aq_frontier_integrate and integrate_mesh of one row,
+    integrate_mesh_batch, mesh_refine, then the first two again: every result is what the same call gives on a fresh
+    context, the meshes bit for bit. Then one plain aq_level_step on a caller-owned frontier folds at once (its
+    accumulator is final once the device is idle, without aq_synchronize): the walks put defer_fold back."""
+    from ppls_amd import Context, Problem
+    from ppls_amd.frontier import HipStepper
+    integrand, a, b, theta, ceps, feps, coarse, fine, rf = mrr.case("edges")
+    assert (a[304], b[304]) == (0.0, 5.0)
+    one = Problem(integrand=integrand, a=0.0, b=5.0, eps=ceps)
+    da, db = _dev(torch, a), _dev(torch, b)
+
+    def host(*tensors):
+        return [t.cpu().numpy().copy() for t in tensors]
+
+    def integral(c):
+        r = HipStepper(c).integrate_one_gpu(one, FRONTIER_CAP)
+        return r.area, r.tasks, r.accepted, r.levels
+
+    def mesh(c):
+        r, x, f, cum, level = c.integrate_mesh(one, cap_nodes=2 * coarse.rows[304].accepted + 1, frontier_cap=FRONTIER_CAP)
+        return (r.area, r.tasks, r.accepted), host(x, f, cum, level)
+
+    def batch(c):
+        return c.integrate_mesh_batch(da, db, ceps, cap_nodes=coarse.n_nodes, frontier_cap=FRONTIER_CAP)
+
+    def arrays(m):
+        return host(m.x, m.f, m.cum, m.level, m.offsets)
+
+    def level_step(c):
+        fin, out = (torch.zeros((4, 4), dtype=torch.float64, device="cuda:0") for _ in range(2))
+        nout = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+        acc = torch.zeros(8, dtype=torch.float64, device="cuda:0")
+        torch.cuda.synchronize()
+        st = HipStepper(c)
+        st.root(integrand, 0.0, 5.0, fin)
+        st.step(integrand, fin, 1, out, 4, ceps, 0, 96, nout, acc)
+        torch.cuda.synchronize()              # every stream of the device, the context's among them: no fold of its own
+        return host(acc, nout, out)
+
+    def same(got, want):
+        assert len(got) == len(want) and all(np.array_equal(_bits(g), _bits(w)) for g, w in zip(got, want))
+
+    with Context(0) as fresh:
+        want_integral = integral(fresh)
+    with Context(0) as fresh:
+        want_mesh = mesh(fresh)
+    with Context(0) as fresh:
+        want_batch = batch(fresh)
+        want_refined = arrays(fresh.mesh_refine(want_batch, feps, cap_nodes=fine.n_nodes, frontier_cap=FRONTIER_CAP))
+        want_batch = arrays(want_batch)
+    with Context(0) as fresh:
+        want_step = level_step(fresh)
+    assert want_step[0][2] == 1 and want_step[1][0] == 2      # the root's task, folded; its two children
+    assert want_integral[1:] == (coarse.rows[304].tasks, coarse.rows[304].accepted, coarse.rows[304].levels)
+
+    with Context(0) as c:
+        assert integral(c) == want_integral
+        got = mesh(c)
+        assert got[0] == want_mesh[0]
+        same(got[1], want_mesh[1])
+        built = batch(c)
+        same(arrays(built), want_batch)
+        refined = c.mesh_refine(built, feps, cap_nodes=fine.n_nodes, frontier_cap=FRONTIER_CAP)
+        same(arrays(refined), want_refined)
+        assert (refined.evaluated, refined.reseeded) == (rf.evaluated, rf.reseeded)
+        assert integral(c) == want_integral
+        got = mesh(c)
+        assert got[0] == want_mesh[0]
+        same(got[1], want_mesh[1])
+        same(level_step(c), want_step)
+
+
 def _err(ctx, torch, off, x, f, n):
     ea, es = (torch.full((n,), POISON, dtype=torch.float64, device="cuda:0") for _ in range(2))
     torch.cuda.synchronize()

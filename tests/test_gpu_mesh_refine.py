@@ -19,7 +19,7 @@ TESTS = [("test_parity", 4), ("test_two_hops_equal_one_and_the_build", 1), ("tes
          ("test_no_op_at_the_inputs_eps_and_above", 1), ("test_edges_when_a_workgroup_takes_several_chunks", 1),
          ("test_capacities_and_depth", 1), ("test_refused_arguments", 1),
          ("test_rows_without_nodes_and_device_memory", 1), ("test_err_sums", 3), ("test_tolerance_driven_meshes", 2),
-         ("test_tolerance_with_an_invalid_row", 1)]
+         ("test_tolerance_with_an_invalid_row", 1), ("test_walks_interleaved_on_one_context", 1)]
 
 
 @pytest.fixture(scope="module")
