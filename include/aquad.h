@@ -597,7 +597,7 @@ int aq_mesh_invert_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const
  * (no float atomics), so a row's sums are bit-identical from run to run and in whatever batch the row sits. A row
  * without nodes gives NaN. Either output may be NULL. The call only enqueues on the context's stream; its scratch
  * is context-owned. AQ_EINVAL: a NULL ctx, or a NULL input with n > 0.
- * Not covered: the single-mesh form (a batch of one row serves), shards and groups, coarsening, the CLI, a C form
+ * Not covered: the single-mesh form (a batch of one row serves), shards and groups, the CLI, a C form
  * of the tolerance loop (Context.integrate_mesh_batch_tol drives these two calls round by round). */
 typedef struct {
     uint64_t n_nodes, leaves, tasks;   /* of the OUTPUT meshes; tasks = 2 * leaves - rows with nodes */
@@ -611,6 +611,64 @@ int aq_mesh_refine_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const
                          uint64_t cap_nodes, aq_mesh_refine_info *info);
 int aq_mesh_err_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
                       double *d_err_abs, double *d_err_signed);
+
+/* ---- mesh coarsening: any coarser mesh, or a leaf budget, from a fine mesh ----------------------------
+ * The converse of refinement: the tree at eps' >= eps is a sub-tree of the tree at eps, and everything its tasks
+ * computed is stored in the fine mesh as node values, so every coarser mesh of a batch mesh (d_offsets [n + 1], d_x,
+ * d_f, d_level [offsets[n]]; cum is not read) follows from the node arrays alone: no integrand, no theta, whatever
+ * eps each row was built with. All pointers are DEVICE memory of the context's device. The three calls block; the
+ * inputs are not validated (as the query calls do not validate theirs), but every index a kernel forms stays inside
+ * its row's slice whatever bytes d_level holds.
+ * Thresholds. An interior even node k of a row is the midpoint of exactly one internal node T of the row's tree;
+ * thr[k] is the minimum over T and its ancestors of |d| = fabs((larea + rarea) - lrarea), the task step's three
+ * expressions on the stored values, one IEEE operation each. aq_mesh_thresholds_batch writes, for k a node of row i
+ * (local index, m_i the last): +inf at k == 0 and k == m_i, 0 at odd k, the threshold at even interior k. So x[k]
+ * is a leaf bound of the row's mesh at eps' iff thr[k] > eps', for every eps' >= 0 (the strict > of the task step).
+ * Budget. aq_mesh_budget_batch writes eps[i] = -1.0 when row i has at most max_leaves leaves (or no nodes), else
+ * the max_leaves-th largest (1-based) threshold among its even interior nodes: coarsened at that eps the row has the
+ * largest leaf count <= max_leaves that any eps gives -- exactly max_leaves unless thresholds tie there.
+ * max_leaves >= 1, else AQ_EINVAL.
+ * Coarsening. aq_mesh_coarsen_batch coarsens row i at e_i = d_eps ? d_eps[i] : eps; a row whose e_i is negative or
+ * NaN is copied unchanged (the mask, and the -1 the budget call writes); a scalar eps that is negative or NaN with
+ * d_eps == NULL is AQ_EINVAL. d_thr: the thresholds call's output, or NULL (computed into context scratch).
+ * For e_i no smaller than the eps the row was built with, row i of `out` is the mesh aq_integrate_mesh_batch defines
+ * at e_i: offsets, x, f, level, accepted, tasks and status bit for bit, every cum value within that call's bound
+ * (restarting per row), and cum bit for bit that call's whenever every row holds the leaves one build would give (one
+ * eps for all rows). For a smaller e_i nothing merges: the output row is the input row. A row without nodes stays
+ * without nodes: AQ_ROW_INVALID, area NaN, accepted = tasks = 0. out->a, out->b, out->theta and out->max_depth are
+ * ignored; the inputs must not overlap the outputs.
+ * info: n_nodes, leaves and tasks (= 2 * leaves - rows with nodes) of the OUTPUT; merged = input leaves - output
+ * leaves; levels = the deepest output level + 1.
+ * Capacity. n_nodes > cap_nodes: AQ_EOVERFLOW with info->n_nodes reported and nothing written at or past cap_nodes
+ * (offsets and the node arrays are then unspecified). The input's node count always suffices.
+ * AQ_EINVAL: a NULL ctx, out, info, out->offsets, out->x, out->f or out->cum; a NULL input array with n > 0 (d_thr of
+ * the thresholds and budget calls and d_eps of the budget call among them); cap_nodes < 3 or > 2^31; an input of more
+ * than 2^31 nodes; n > 0x7fffffff. n == 0: AQ_OK, info zeroed, nothing enqueued.
+ * Determinism. Every output of the three calls is bit-identical from run to run: the positions are an integer scan
+ * without atomics, the thresholds a minimum, and the leaves are sorted by (row, l) before they are laid out.
+ * Host looks. Each call reads the input's node count, offsets[n], first; the coarsen call also reads its output's
+ * leaf count before the layout.
+ * Device memory. 16 bytes of position per leaf, with its row, |d| and parent index (16 bytes more), the threshold
+ * scratch when d_thr is NULL, and for the budget the mesh's sort arrays over the nodes; the coarsen call borrows the
+ * leaf buffer and sort arrays of aq_integrate_mesh_batch. All of it is context-owned, allocated by the first of
+ * these calls and grown on demand; aq_ctx_device_bytes does not move before that call, nor at a second call of the
+ * same sizes.
+ * Not covered: meshes from the persistent kernel, shards and groups, the CLI, a per-row max_leaves, enqueue-only
+ * forms; a batch of few, huge rows -- the position scan runs one workgroup per row (a row's leaves / 256 steps in
+ * turn) and the head of a merged leaf walks the leaves merged into it alone, so such a batch serialises; the calls are
+ * for batches of many rows (the largest row measured has 15 573 leaves). */
+typedef struct {
+    uint64_t n_nodes, leaves, tasks;   /* of the OUTPUT meshes; tasks = 2 * leaves - rows with nodes */
+    uint64_t merged;                   /* input leaves - output leaves */
+    uint32_t levels, reserved;         /* deepest level + 1 of the output trees */
+} aq_mesh_coarsen_info;
+int aq_mesh_thresholds_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                             const uint8_t *d_level, double *d_thr);
+int aq_mesh_budget_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_thr, uint64_t max_leaves,
+                         double *d_eps);
+int aq_mesh_coarsen_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                          const uint8_t *d_level, const double *d_thr, const double *d_eps, double eps,
+                          const aq_mesh_batch_io *out, uint64_t cap_nodes, aq_mesh_coarsen_info *info);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel, and of aq_mesh_invert's kernel, on

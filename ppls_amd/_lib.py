@@ -28,6 +28,7 @@ EXPORTS = (
     "aq_integrate_mesh", "aq_mesh_eval", "aq_mesh_invert",
     "aq_integrate_mesh_batch", "aq_mesh_eval_batch", "aq_mesh_invert_batch",
     "aq_mesh_refine_batch", "aq_mesh_err_batch",
+    "aq_mesh_thresholds_batch", "aq_mesh_budget_batch", "aq_mesh_coarsen_batch",
 )
 
 AQ_MAX_LEVELS = 128
@@ -90,6 +91,11 @@ class aq_mesh_refine_info(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
                 ("evaluated", ctypes.c_uint64), ("reseeded", ctypes.c_uint64), ("levels", ctypes.c_uint32),
                 ("widest_level", ctypes.c_uint32)]
+
+
+class aq_mesh_coarsen_info(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
+                ("merged", ctypes.c_uint64), ("levels", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 _lib = None
@@ -191,6 +197,10 @@ def load(build_if_missing=True):
                                   ctypes.POINTER(aq_mesh_batch_io), ctypes.c_uint32, c_int, ctypes.c_uint64,
                                   ctypes.POINTER(aq_mesh_refine_info)], c_int),
         "aq_mesh_err_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp], c_int),
+        "aq_mesh_thresholds_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp], c_int),
+        "aq_mesh_budget_batch": ([vp, ctypes.c_size_t, vp, vp, ctypes.c_uint64, vp], c_int),
+        "aq_mesh_coarsen_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, c_dbl, ctypes.POINTER(aq_mesh_batch_io),
+                                   ctypes.c_uint64, ctypes.POINTER(aq_mesh_coarsen_info)], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -99,7 +99,8 @@ class MeshBatch:
     (float64: the row's last cum, NaN for an invalid row), accepted, tasks (int64) and status (int32: 0 or ROW_*
     bits); and the run's n_nodes, leaves, total_tasks, invalid_rows, levels, widest_level. It also records what it was
     built with -- integrand, theta, eps, max_depth -- which Context.mesh_refine continues from; a mesh that
-    mesh_refine returned carries that call's eps, evaluated and reseeded as well."""
+    mesh_refine returned carries that call's eps, evaluated and reseeded as well, one that mesh_coarsen returned its
+    eps (a float, or the per-row tensor) and merged; no frontier is walked there, so its widest_level is None."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -796,6 +797,93 @@ class Context:
                                         err_abs.data_ptr(), err_signed.data_ptr()), "aq_mesh_err_batch")
         self.synchronize()
         return err_abs, err_signed
+
+    # -- mesh coarsening: any coarser mesh, or a leaf budget, from a fine mesh ------------------
+    def _coarsen_inputs(self, mesh):
+        import torch
+        dev = torch.device("cuda", self.device)
+        for t, what, dt in ((mesh.offsets, "mesh.offsets", torch.int64), (mesh.x, "mesh.x", torch.float64),
+                            (mesh.f, "mesh.f", torch.float64), (mesh.level, "mesh.level", torch.uint8)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dt} tensor on {dev}")
+        m = int(mesh.x.shape[0])
+        if mesh.f.shape[0] != m or mesh.level.shape[0] != m:
+            raise ValueError("mesh.x, mesh.f and mesh.level must have one length")
+        return dev, len(mesh), m
+
+    def mesh_thresholds(self, mesh: MeshBatch):
+        """The thresholds of a MeshBatch (aq_mesh_thresholds_batch), a float64 CUDA tensor of n_nodes: x[k] is a leaf
+        bound of its row's mesh at eps' exactly when thr[k] > eps' -- +inf at a row's two ends, 0 at its odd nodes.
+        Computed from the node arrays alone: no integrand, no theta. One array serves every eps and every budget."""
+        import torch
+        dev, n, m = self._coarsen_inputs(mesh)
+        thr = torch.empty(m, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.L.aq_mesh_thresholds_batch(self._h, n, mesh.offsets.data_ptr(), mesh.x.data_ptr(), mesh.f.data_ptr(),
+                                               mesh.level.data_ptr(), thr.data_ptr()), "aq_mesh_thresholds_batch")
+        return thr
+
+    def mesh_coarsen(self, mesh: MeshBatch, eps=None, max_leaves=None, thr=None, cap_nodes=None) -> MeshBatch:
+        """The meshes of `mesh`'s rows at a larger eps, or with at most max_leaves leaves per row, without one
+        evaluation of F (aq_mesh_coarsen_batch). Exactly one of eps / max_leaves: eps is a float, or a float64 CUDA
+        tensor (n,) with one eps per row (negative or NaN: the row is copied); max_leaves runs thresholds -> budget
+        (aq_mesh_budget_batch: the row's max_leaves-th largest threshold, -1 for a row that is small enough) ->
+        coarsen. thr: mesh_thresholds(mesh), to reuse it over several calls. cap_nodes=None: the input's node count,
+        which always suffices. Returns a new MeshBatch (integrand, theta and max_depth the input's; eps the float, or
+        the per-row tensor that was used) with `merged`, the leaves that went. Blocks."""
+        import torch
+        dev, n, m_in = self._coarsen_inputs(mesh)
+        if (eps is None) == (max_leaves is None):
+            raise ValueError("exactly one of eps and max_leaves must be given")
+        if thr is not None and not (isinstance(thr, torch.Tensor) and thr.is_cuda and thr.device == dev and
+                                    thr.dtype == torch.float64 and thr.is_contiguous() and tuple(thr.shape) == (m_in,)):
+            raise ValueError(f"thr must be a contiguous float64 tensor of shape ({m_in},) on {dev}")
+        row_eps = None
+        if max_leaves is not None:
+            if int(max_leaves) < 1:
+                raise ValueError("max_leaves must be at least 1")
+            if thr is None:
+                thr = self.mesh_thresholds(mesh)
+            row_eps = torch.empty(n, dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            _check(self.L.aq_mesh_budget_batch(self._h, n, mesh.offsets.data_ptr(), thr.data_ptr(), int(max_leaves),
+                                               row_eps.data_ptr()), "aq_mesh_budget_batch")
+        elif isinstance(eps, torch.Tensor):
+            if not (eps.is_cuda and eps.device == dev and eps.dtype == torch.float64 and eps.is_contiguous() and
+                    tuple(eps.shape) == (n,)):
+                raise ValueError(f"eps must be a float, or a contiguous float64 tensor of shape ({n},) on {dev}")
+            row_eps = eps
+        cap_nodes = max(m_in, 3) if cap_nodes is None else int(cap_nodes)
+        if cap_nodes < 3:
+            raise ValueError("cap_nodes must be at least 3")
+        x, f, cum = (torch.empty(cap_nodes, dtype=torch.float64, device=dev) for _ in range(3))
+        level = torch.empty(cap_nodes, dtype=torch.uint8, device=dev)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        area = torch.empty(n, dtype=torch.float64, device=dev)
+        accepted, tasks = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2))
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        max_depth = int(mesh.max_depth)
+        io = _lib.aq_mesh_batch_io(None, None, None, ptr(offsets), ptr(x), ptr(f), ptr(cum), ptr(level), ptr(area),
+                                   ptr(accepted), ptr(tasks), ptr(status), max_depth, 0)
+        info = _lib.aq_mesh_coarsen_info()
+        rc = self.L.aq_mesh_coarsen_batch(self._h, n, ptr(mesh.offsets), ptr(mesh.x), ptr(mesh.f), ptr(mesh.level),
+                                          ptr(thr), ptr(row_eps), 0.0 if row_eps is not None else float(eps),
+                                          ctypes.byref(io), cap_nodes, ctypes.byref(info))
+        if rc == -4 and info.n_nodes:   # AQ_EOVERFLOW of cap_nodes
+            e = AquadError(f"aq_mesh_coarsen_batch: the meshes have {info.n_nodes} nodes, cap_nodes is {cap_nodes} "
+                           f"(code {rc})", rc)
+            e.n_nodes = int(info.n_nodes)
+            raise e
+        _check(rc, "aq_mesh_coarsen_batch")
+        m = int(info.n_nodes)
+        return MeshBatch(offsets=offsets, x=x[:m], f=f[:m], cum=cum[:m], level=level[:m], area=area, accepted=accepted,
+                         tasks=tasks, status=status, n_nodes=m, leaves=int(info.leaves), total_tasks=int(info.tasks),
+                         invalid_rows=n - (m - 2 * int(info.leaves)), levels=int(info.levels), widest_level=None,
+                         integrand=mesh.integrand, theta=mesh.theta,
+                         eps=row_eps if row_eps is not None else float(eps), max_depth=max_depth,
+                         merged=int(info.merged))
 
     def integrate_mesh_batch_tol(self, a, b, epsabs=0.0, epsrel=0.0, eps0=1e-3, shrink=8.0, max_rounds=12,
                                  integrand=COSH4, theta=None, max_depth=0, cap_nodes=None, frontier_cap=1 << 22,

@@ -287,6 +287,12 @@ struct MeshBufs {
     PinBuf<unsigned> h_rtab;                       // pinned copy
     PinBuf<unsigned long long> h_rnodes;           // pinned: the input's node count (one word)
     DevBuf<double4> d_eparts{bytes};               // aq_mesh_err_batch's block partials (its first call)
+    // mesh coarsening (aq_mesh_thresholds_batch, aq_mesh_budget_batch, aq_mesh_coarsen_batch)
+    DevBuf<ulonglong2> d_cpos{bytes};              // a leaf's 128-bit position, at slot (its first node) >> 1
+    DevBuf<unsigned> d_crow{bytes};                // ... its row (0xffffffff: no leaf's slot)
+    DevBuf<double> d_cdabs{bytes};                 // ... |d| of the internal node whose midpoint the leaf starts at
+    DevBuf<unsigned> d_cpar{bytes};                // ... and the leaf at that node's parent's midpoint (0: none)
+    DevBuf<double> d_cthr{bytes};                  // the thresholds, when the caller passes none
 
     // the leaf buffer of a run that may emit cap_leaves, and its count
     int ensure_leaves(size_t cap_leaves) {
@@ -324,6 +330,17 @@ struct MeshBufs {
             AQ_HIP(h_rtab.grow(REFINE_TAB_WORDS));
             AQ_HIP(h_rnodes.grow(1));
         }
+        return AQ_OK;
+    }
+    // the thresholds of a mesh of m nodes (own_thr: into d_cthr)
+    int ensure_coarsen(size_t m, bool own_thr) {
+        const size_t slots = (m + 1) / 2;
+        AQ_HIP(h_rnodes.grow(1));
+        AQ_HIP(d_cpos.grow(slots));
+        AQ_HIP(d_crow.grow(slots));
+        AQ_HIP(d_cdabs.grow(slots));
+        AQ_HIP(d_cpar.grow(slots));
+        if (own_thr) AQ_HIP(d_cthr.grow(m));
         return AQ_OK;
     }
 };
@@ -2658,6 +2675,171 @@ int aq_mesh_err_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const do
                        d_err_signed);
     AQ_HIP(hipGetLastError());
     return AQ_OK;
+}
+
+// Mesh coarsening (aquad.hip k_mesh_coarsen_*, k_mesh_budget_*). The three calls block, and each begins with one host
+// look: the input's node count, offsets[n].
+static int coarsen_nodes(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, unsigned long long* m_in) {
+    MeshBufs& mb = ctx->mesh;
+    AQ_HIP(mb.h_rnodes.grow(1));
+    AQ_HIP(hipMemcpyAsync(mb.h_rnodes, d_offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    *m_in = mb.h_rnodes[0];
+    return *m_in > (1ull << 31) ? AQ_EINVAL : AQ_OK;
+}
+
+// The leaves' positions and rows of `in` (n_nodes > 0) into the context's scratch, enqueued.
+static int coarsen_positions(aq_ctx* ctx, const CoarsenIn& in) {
+    MeshBufs& mb = ctx->mesh;
+    const unsigned long long slots = (in.n_nodes + 1) / 2;
+    AQ_HIP(hipMemsetAsync(mb.d_crow, 0xff, sizeof(unsigned) * slots, ctx->stream));
+    hipLaunchKernelGGL(k_mesh_coarsen_pos, dim3(in.n_rows), dim3(COARSEN_T), 0, ctx->stream, in, mb.d_cpos.get(),
+                       mb.d_crow.get());
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+// The thresholds of `in` (n_nodes > 0) into thr, enqueued; the positions and rows stay in the context's scratch.
+static int coarsen_thresholds(aq_ctx* ctx, const CoarsenIn& in, double* thr) {
+    MeshBufs& mb = ctx->mesh;
+    const unsigned long long slots = (in.n_nodes + 1) / 2;
+    const unsigned sgrid = (unsigned)((slots + COARSEN_T - 1) / COARSEN_T);
+    if (int rc = coarsen_positions(ctx, in)) return rc;
+    hipLaunchKernelGGL(k_mesh_coarsen_node, dim3(sgrid), dim3(COARSEN_T), 0, ctx->stream, in, slots,
+                       (const ulonglong2*)mb.d_cpos.get(), (const unsigned*)mb.d_crow.get(), mb.d_cdabs.get(),
+                       mb.d_cpar.get());
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_coarsen_thr, dim3(sgrid), dim3(COARSEN_T), 0, ctx->stream, in, slots,
+                       (const unsigned*)mb.d_crow.get(), (const double*)mb.d_cdabs.get(), (const unsigned*)mb.d_cpar.get(),
+                       thr);
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+int aq_mesh_thresholds_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                             const uint8_t* d_level, double* d_thr) {
+    if (!ctx) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_x || !d_f || !d_level || !d_thr)) return AQ_EINVAL;
+    if (n > 0x7fffffffull) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    AQ_HIP(hipSetDevice(ctx->device));
+    unsigned long long m_in = 0;
+    int rc;
+    if ((rc = coarsen_nodes(ctx, n, d_offsets, &m_in))) return rc;
+    if (m_in == 0) return AQ_OK;
+    if ((rc = ctx->mesh.ensure_coarsen(m_in, false))) return rc;
+    const CoarsenIn in{(const unsigned long long*)d_offsets, d_x, d_f, d_level, (unsigned)n, m_in};
+    if ((rc = coarsen_thresholds(ctx, in, d_thr))) return rc;
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
+// The nodes sorted by (row, key) -- the back half's two passes over the mesh's sort arrays -- then one pick per row.
+int aq_mesh_budget_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_thr, uint64_t max_leaves,
+                         double* d_eps) {
+    if (!ctx || max_leaves < 1) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_thr || !d_eps)) return AQ_EINVAL;
+    if (n > 0x7fffffffull) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    AQ_HIP(hipSetDevice(ctx->device));
+    MeshBufs& mb = ctx->mesh;
+    unsigned long long m_in = 0;
+    int rc;
+    if ((rc = coarsen_nodes(ctx, n, d_offsets, &m_in))) return rc;
+    const unsigned nr = (unsigned)n;
+    const unsigned long long* off = (const unsigned long long*)d_offsets;
+    const unsigned* idx = nullptr;
+    if (m_in > 0) {
+        const unsigned grid = (unsigned)((m_in + COARSEN_T - 1) / COARSEN_T);
+        unsigned bits = 0;
+        while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;   // ceil(log2 n): the rows are < n
+        hipError_t he = hipSuccess;
+        size_t sort_bytes = mesh_sort_scratch_bytes(m_in, &he);
+        AQ_HIP(he);
+        if (n > 1) {
+            sort_bytes = std::max(sort_bytes, mesh_sort_rows_scratch_bytes(m_in, bits, &he));
+            AQ_HIP(he);
+        }
+        if ((rc = mb.ensure_sort(m_in, sort_bytes, grid, n))) return rc;
+        unsigned* row_of = mb.d_bnode;   // [m_in]: the nodes' rows
+        hipLaunchKernelGGL(k_mesh_budget_keys, dim3(grid), dim3(COARSEN_T), 0, ctx->stream, off, nr, m_in, d_thr,
+                           mb.d_mkey[0].get(), mb.d_midx[0].get(), row_of);
+        AQ_HIP(hipGetLastError());
+        AQ_HIP(mesh_sort(mb.d_msort, sort_bytes, mb.d_mkey[0], mb.d_mkey[1], mb.d_midx[0], mb.d_midx[1], m_in,
+                         ctx->stream));
+        idx = mb.d_midx[1];
+        if (n > 1) {
+            hipLaunchKernelGGL(k_mesh_budget_rowkeys, dim3(grid), dim3(COARSEN_T), 0, ctx->stream, (const unsigned*)row_of,
+                               idx, m_in, mb.d_bkey[0].get());
+            AQ_HIP(hipGetLastError());
+            AQ_HIP(mesh_sort_rows(mb.d_msort, sort_bytes, mb.d_bkey[0], mb.d_bkey[1], mb.d_midx[1], mb.d_midx[0], m_in,
+                                  bits, ctx->stream));
+            idx = mb.d_midx[0];
+        }
+    }
+    hipLaunchKernelGGL(k_mesh_budget_pick, dim3((nr + COARSEN_T - 1) / COARSEN_T), dim3(COARSEN_T), 0, ctx->stream, off, nr,
+                       m_in, d_thr, idx, (unsigned long long)max_leaves, d_eps);
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    return AQ_OK;
+}
+
+// Any coarser mesh from a fine one: the heads' leaf records into the context's leaf buffer, then the back half of
+// aq_integrate_mesh_batch, unchanged. A second host look, behind the emission: the output's leaves.
+int aq_mesh_coarsen_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                          const uint8_t* d_level, const double* d_thr, const double* d_eps, double eps,
+                          const aq_mesh_batch_io* out, uint64_t cap_nodes, aq_mesh_coarsen_info* info) {
+    if (!ctx || !out || !info || !out->offsets || !out->x || !out->f || !out->cum) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_x || !d_f || !d_level)) return AQ_EINVAL;
+    if (!d_eps && !(eps >= 0.0)) return AQ_EINVAL;
+    if (n > 0x7fffffffull || cap_nodes < 3 || cap_nodes > (1ull << 31)) return AQ_EINVAL;
+    *info = aq_mesh_coarsen_info{};
+    if (n == 0) return AQ_OK;
+    AQ_HIP(hipSetDevice(ctx->device));
+    MeshBufs& mb = ctx->mesh;
+    const unsigned nr = (unsigned)n;
+    const size_t cap_leaves = (size_t)(cap_nodes / 2);
+    unsigned long long m_in = 0;
+    int rc;
+    if ((rc = coarsen_nodes(ctx, n, d_offsets, &m_in))) return rc;
+    if ((rc = mb.ensure_batch(n, 0, cap_leaves, !out->status, true))) return rc;   // (no frontier: no row arrays)
+    if ((rc = mb.ensure_coarsen(m_in, !d_thr))) return rc;
+    unsigned* status = out->status ? out->status : mb.d_bstatus.get();
+    unsigned* levels = mb.d_rtab.get() + REFINE_TAB_LEVELS;
+    AQ_HIP(hipMemsetAsync(levels, 0, sizeof(unsigned), ctx->stream));
+    AQ_HIP(hipMemsetAsync(mb.d_leafcnt, 0, sizeof(unsigned long long), ctx->stream));
+    AQ_HIP(hipMemsetAsync(mb.d_binvalid, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_mesh_refine_rows, dim3((nr + REFINE_T - 1) / REFINE_T), dim3(REFINE_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, nr, status, mb.d_binvalid.get());
+    AQ_HIP(hipGetLastError());
+    if (m_in > 0) {
+        const CoarsenIn in{(const unsigned long long*)d_offsets, d_x, d_f, d_level, nr, m_in};
+        const unsigned long long slots = (m_in + 1) / 2;
+        const double* thr = d_thr;
+        if (!thr) {
+            if ((rc = coarsen_thresholds(ctx, in, mb.d_cthr.get()))) return rc;
+            thr = mb.d_cthr;
+        } else if ((rc = coarsen_positions(ctx, in))) {   // the positions and the rows alone
+            return rc;
+        }
+        const LeafSink sink{mb.d_leaf, mb.d_leafcnt, (unsigned long long)cap_leaves};
+        hipLaunchKernelGGL(k_mesh_coarsen_emit, dim3((unsigned)((slots + COARSEN_T - 1) / COARSEN_T)), dim3(COARSEN_T), 0,
+                           ctx->stream, in, slots, (const ulonglong2*)mb.d_cpos.get(), (const unsigned*)mb.d_crow.get(), thr,
+                           d_eps, eps, sink, levels);
+        AQ_HIP(hipGetLastError());
+    }
+    AQ_HIP(hipMemcpyAsync(mb.h_bwords, mb.d_leafcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(mb.h_bwords + 1, mb.d_binvalid, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipMemcpyAsync(mb.h_rtab + REFINE_TAB_LEVELS, levels, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    AQ_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t leaves = mb.h_bwords[0], with_nodes = n - mb.h_bwords[1];
+    info->leaves = leaves;
+    info->tasks = 2 * leaves - with_nodes;
+    info->n_nodes = 2 * leaves + with_nodes;
+    info->merged = (m_in - with_nodes) / 2 - leaves;
+    info->levels = mb.h_rtab[REFINE_TAB_LEVELS];
+    if (info->n_nodes > cap_nodes) return AQ_EOVERFLOW;
+    return mesh_batch_back(ctx, n, out, (unsigned)leaves);
 }
 
 int aq_mesh_eval(aq_ctx* ctx, uint64_t n_nodes, const double* d_x, const double* d_f, const double* d_cum, size_t nq,

@@ -1569,6 +1569,296 @@ __global__ __launch_bounds__(MESH_T) void k_mesh_err_finish(const unsigned long 
     if (err_signed) err_signed[i] = none ? nan : SH + SL;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Mesh coarsening (aq_mesh_thresholds_batch, aq_mesh_budget_batch, aq_mesh_coarsen_batch): the converse of
+// refinement. The tree at eps' >= eps is a sub-tree of the tree at eps, and every value its tasks computed is a
+// node value of the fine mesh, so any coarser mesh follows from the node arrays alone -- no F, no theta.
+// Leaf j of a row (x order, depth lev_j) starts at the position pos_j = sum_{i<j} 2^(127 - lev_i), an exact 128-bit
+// integer (the row ends at 2^127). The tree node of depth k over leaf j starts at pos_j with its low 127 - k bits
+// cleared; a leaf j >= 1 starts at the midpoint of exactly one internal node N(j), of depth 126 - ctz(pos_j).
+//   k_mesh_coarsen_pos    one block per row: the exclusive scan of 2^(127 - lev) over the row's leaves, chunk after
+//                         chunk of COARSEN_T (wave shuffles, the waves' totals in LDS, an integer carry: no atomics);
+//                         it also writes every leaf's row beside its position
+//   k_mesh_coarsen_node   one leaf j >= 1 per thread: N(j)'s start and end by two clamped searches of the row's
+//                         positions, |d| = fabs((larea + rarea) - lrarea) from the six node values (the task step's
+//                         expressions), and N(j)'s parent: N(il) when N(j) is a right child, else N(ir)
+//   k_mesh_coarsen_thr    thr = the minimum of |d| over N(j) and its ancestors (the parent chain, at most
+//                         AQ_MAX_LEVELS loads); +inf at a row's two ends, 0 at its odd nodes. x[k] bounds a leaf of
+//                         the row's mesh at eps' iff thr[k] > eps'
+//   k_mesh_coarsen_emit   a head (the row's first leaf, or thr > the row's eps; every leaf of a row whose eps is
+//                         negative or NaN) emits ONE leaf record as k_mesh_refine_classify does: r from the next
+//                         head (a forward walk bounded by the row's end), the depth from the position difference,
+//                         F(mid) from one search. The back half of aq_integrate_mesh_batch lays the records out.
+//   k_mesh_budget_keys / _rowkeys / _pick   the row's max_leaves-th largest threshold: the nodes sorted by (row,
+//                         key), key = thr at an even interior node and 0 elsewhere (aq_mesh_sort.hip, two passes)
+// A leaf's scratch slot is (its first node) >> 1: a row of L leaves at offset o0 owns the slots [o0 >> 1, (o0 >> 1) + L),
+// which no other row's leaf maps to (a row has 2 L + 1 nodes). Every index below is clamped into its row's slice, so
+// `level` may hold any bytes.
+// ------------------------------------------------------------------------------------------------
+constexpr int COARSEN_T = 256;
+constexpr int COARSEN_NW = COARSEN_T / 64;
+
+struct U128 {
+    unsigned long long lo, hi;
+};
+__device__ __forceinline__ U128 u128_add(U128 a, U128 b) {
+    U128 r;
+    r.lo = a.lo + b.lo;
+    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1ull : 0ull);
+    return r;
+}
+__device__ __forceinline__ U128 u128_sub(U128 a, U128 b) {
+    U128 r;
+    r.lo = a.lo - b.lo;
+    r.hi = a.hi - b.hi - (a.lo < b.lo ? 1ull : 0ull);
+    return r;
+}
+__device__ __forceinline__ bool u128_lt(U128 a, U128 b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+__device__ __forceinline__ U128 u128_pow2(unsigned e) {   // e <= 127
+    return U128{e < 64u ? 1ull << e : 0ull, e >= 64u ? 1ull << (e - 64u) : 0ull};
+}
+__device__ __forceinline__ U128 u128_half(U128 a) { return U128{(a.lo >> 1) | (a.hi << 63), a.hi >> 1}; }
+__device__ __forceinline__ unsigned u128_ctz(U128 a) {   // 128 for 0
+    return a.lo ? (unsigned)__ffsll((unsigned long long)a.lo) - 1u : a.hi ? 63u + (unsigned)__ffsll((unsigned long long)a.hi) : 128u;
+}
+__device__ __forceinline__ unsigned u128_clz(U128 a) {   // 128 for 0
+    return a.hi ? (unsigned)__clzll((long long)a.hi) : a.lo ? 64u + (unsigned)__clzll((long long)a.lo) : 128u;
+}
+__device__ __forceinline__ U128 u128_of(ulonglong2 v) { return U128{v.x, v.y}; }
+
+struct CoarsenIn {   // the input mesh
+    const unsigned long long* off;
+    const double* x;
+    const double* f;
+    const unsigned char* level;
+    unsigned n_rows;
+    unsigned long long n_nodes;    // off[n_rows], read by the host
+};
+
+// The leaves of a row of nodes [o0, o1) (none below 3 nodes).
+__device__ __forceinline__ unsigned coarsen_leaves(unsigned long long o0, unsigned long long o1) {
+    return o1 >= o0 + 3 ? (unsigned)((o1 - o0 - 1) / 2) : 0u;
+}
+
+// The first index in [lo, hi) of the row's positions that is not below `key`, or hi.
+__device__ __forceinline__ unsigned coarsen_lower_bound(const ulonglong2* __restrict__ p, unsigned lo, unsigned hi, U128 key) {
+    while (lo < hi) {
+        const unsigned m = lo + (hi - lo) / 2;
+        if (u128_lt(u128_of(p[m]), key)) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+
+// Slot s of the scratch arrays: false unless it is a leaf's. Otherwise its row, the row's first node and first slot,
+// its leaves, and the leaf's index in the row.
+__device__ __forceinline__ bool coarsen_slot(const CoarsenIn& in, const unsigned* __restrict__ rowof, unsigned long long s,
+                                             unsigned long long n_slots, unsigned& row, unsigned long long& o0,
+                                             unsigned long long& sb, unsigned& L, unsigned& j) {
+    if (s >= n_slots) return false;
+    row = rowof[s];
+    if (row >= in.n_rows) return false;   // 0xffffffff: no leaf's slot (rows are < 2^31)
+    o0 = in.off[row];
+    L = coarsen_leaves(o0, in.off[row + 1]);
+    sb = o0 >> 1;
+    if (s < sb || s - sb >= L) return false;
+    j = (unsigned)(s - sb);
+    return true;
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_coarsen_pos(CoarsenIn in, ulonglong2* __restrict__ pos,
+                                                                 unsigned* __restrict__ rowof) {
+    __shared__ U128 s_w[COARSEN_NW];
+    const unsigned row = blockIdx.x;
+    const unsigned long long o0 = in.off[row], o1 = in.off[row + 1];
+    const unsigned L = o1 <= in.n_nodes ? coarsen_leaves(o0, o1) : 0u;
+    const unsigned long long sb = o0 >> 1;
+    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
+    U128 carry{0ull, 0ull};   // the chunks before this one (the same in every thread)
+    for (unsigned c = 0; c < L; c += COARSEN_T) {
+        const unsigned j = c + threadIdx.x;
+        U128 v{0ull, 0ull};
+        if (j < L) v = u128_pow2(127u - min((unsigned)in.level[o0 + 2ull * j], 127u));
+        U128 inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const U128 up{__shfl_up(inc.lo, o, 64), __shfl_up(inc.hi, o, 64)};
+            if (lane >= (unsigned)o) inc = u128_add(inc, up);
+        }
+        if (lane == 63) s_w[w] = inc;
+        __syncthreads();
+        U128 pre{0ull, 0ull}, tot{0ull, 0ull};   // the waves before this one, in order
+        for (unsigned v2 = 0; v2 < (unsigned)COARSEN_NW; ++v2) {
+            if (v2 == w) pre = tot;
+            tot = u128_add(tot, s_w[v2]);
+        }
+        if (j < L) {
+            const U128 p = u128_add(carry, u128_add(pre, u128_sub(inc, v)));
+            pos[sb + j] = make_ulonglong2(p.lo, p.hi);
+            rowof[sb + j] = row;
+        }
+        carry = u128_add(carry, tot);
+        __syncthreads();   // s_w is written again
+    }
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_coarsen_node(CoarsenIn in, unsigned long long n_slots,
+                                                                  const ulonglong2* __restrict__ pos,
+                                                                  const unsigned* __restrict__ rowof,
+                                                                  double* __restrict__ dabs, unsigned* __restrict__ par) {
+    const unsigned long long s = (unsigned long long)blockIdx.x * COARSEN_T + threadIdx.x;
+    unsigned row, L, j;
+    unsigned long long o0, sb;
+    if (!coarsen_slot(in, rowof, s, n_slots, row, o0, sb, L, j) || j == 0u) return;
+    const ulonglong2* rp = pos + sb;
+    const U128 p = u128_of(rp[j]);
+    const unsigned tz = min(u128_ctz(p), 126u);           // N(j)'s depth is 126 - tz
+    const U128 start = u128_sub(p, u128_pow2(tz));        // p with its low tz + 1 bits cleared
+    const U128 end = u128_add(start, u128_pow2(tz + 1u));
+    const unsigned il = min(coarsen_lower_bound(rp, 0u, j, start), j - 1u);   // < j
+    const unsigned ir = coarsen_lower_bound(rp, j + 1u, L, end);              // in (j, L]: L is the row's last node
+    const unsigned long long kl = o0 + 2ull * il, km = o0 + 2ull * j, kr = o0 + 2ull * ir;
+    const double l = in.x[kl], mid = in.x[km], r = in.x[kr], fl = in.f[kl], fmid = in.f[km], fr = in.f[kr];
+    const double lrarea = (fl + fr) * (r - l) / 2;        // :185
+    const double larea = (fl + fmid) * (mid - l) / 2;     // :189
+    const double rarea = (fmid + fr) * (r - mid) / 2;     // :190
+    dabs[s] = fabs((larea + rarea) - lrarea);             // :191
+    unsigned q = 0u;                                      // 0: no parent (leaf 0 starts at no node's midpoint)
+    if (tz < 126u) {
+        const U128 bit = u128_pow2(tz + 1u);              // set in `start`: N(j) is a right child, its parent's mid is `start`
+        const bool right = ((start.lo & bit.lo) | (start.hi & bit.hi)) != 0ull;
+        q = right ? il : ir;
+        if (q >= L || q == j) q = 0u;
+    }
+    par[s] = q;
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_coarsen_thr(CoarsenIn in, unsigned long long n_slots,
+                                                                 const unsigned* __restrict__ rowof,
+                                                                 const double* __restrict__ dabs,
+                                                                 const unsigned* __restrict__ par, double* __restrict__ thr) {
+    const unsigned long long s = (unsigned long long)blockIdx.x * COARSEN_T + threadIdx.x;
+    unsigned row, L, j;
+    unsigned long long o0, sb;
+    if (!coarsen_slot(in, rowof, s, n_slots, row, o0, sb, L, j)) return;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    double t = inf;
+    if (j > 0u) {
+        t = dabs[s];
+        unsigned q = par[s];
+        for (int it = 0; it < AQ_MAX_LEVELS && q != 0u; ++it) {
+            t = fmin(t, dabs[sb + q]);
+            q = par[sb + q];
+        }
+    }
+    const unsigned long long k = o0 + 2ull * j;
+    thr[k] = t;
+    thr[k + 1] = 0.0;
+    if (j + 1u == L) thr[k + 2] = inf;
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_coarsen_emit(CoarsenIn in, unsigned long long n_slots,
+                                                                  const ulonglong2* __restrict__ pos,
+                                                                  const unsigned* __restrict__ rowof,
+                                                                  const double* __restrict__ thr,
+                                                                  const double* __restrict__ row_eps, double eps,
+                                                                  LeafSink sink, unsigned* __restrict__ levels) {
+    __shared__ unsigned s_wl[COARSEN_NW], s_levels;
+    __shared__ unsigned long long s_lbase;
+    if (threadIdx.x == 0) s_levels = 0u;
+    __syncthreads();
+    const unsigned long long s = (unsigned long long)blockIdx.x * COARSEN_T + threadIdx.x;
+    unsigned row, L, j;
+    unsigned long long o0, sb;
+    bool head = false;
+    Leaf lf{};
+    if (coarsen_slot(in, rowof, s, n_slots, row, o0, sb, L, j)) {
+        const double e = row_eps ? row_eps[row] : eps;
+        const bool all = !(e >= 0.0);   // negative or NaN: the row is copied
+        head = j == 0u || all || thr[o0 + 2ull * j] > e;
+        if (head) {
+            unsigned jn = j + 1u;       // the next head, or the row's end
+            if (!all) while (jn < L && !(thr[o0 + 2ull * jn] > e)) ++jn;
+            const ulonglong2* rp = pos + sb;
+            const unsigned long long k = o0 + 2ull * j, kn = o0 + 2ull * jn;
+            unsigned depth = in.level[k];
+            double fmid = in.f[k + 1];
+            if (jn > j + 1u) {          // merged: a tree node of 2^(127 - depth) positions, its mid at their half
+                const U128 pj = u128_of(rp[j]);
+                const U128 width = u128_sub(jn < L ? u128_of(rp[jn]) : u128_pow2(127u), pj);
+                depth = min(u128_clz(width), 127u);
+                const unsigned jm = min(coarsen_lower_bound(rp, j + 1u, jn, u128_add(pj, u128_half(width))), jn - 1u);
+                fmid = in.f[o0 + 2ull * jm];
+            }
+            lf = Leaf{in.x[k], in.x[kn], in.f[k], fmid, in.f[kn], (unsigned long long)depth | ((unsigned long long)row << 32)};
+            atomicMax(&s_levels, depth + 1u);
+        }
+    }
+    const unsigned long long mk = __ballot(head);
+    const unsigned w = threadIdx.x >> 6;
+    if (lane_id() == 0) s_wl[w] = (unsigned)__popcll(mk);
+    __syncthreads();
+    if (threadIdx.x == 0) {   // one atomic for the block's leaves (64-bit: the count goes on past the capacity)
+        unsigned tot = 0;
+        for (int v = 0; v < COARSEN_NW; ++v) tot += s_wl[v];
+        s_lbase = tot ? atomicAdd(sink.count, (unsigned long long)tot) : 0ull;
+        if (s_levels) atomicMax(levels, s_levels);
+    }
+    __syncthreads();
+    if (head) {
+        unsigned long long p = s_lbase + mbcnt(mk);
+        for (unsigned v = 0; v < w; ++v) p += s_wl[v];
+        if (p < sink.cap) sink.buf[p] = lf;
+    }
+}
+
+// Node k's row: the last row that starts at or before k (rows without nodes start where the next one does).
+__device__ __forceinline__ unsigned coarsen_row_of(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                   unsigned long long k) {
+    unsigned lo = 0, hi = n_rows - 1;
+    while (lo < hi) {
+        const unsigned m = lo + (hi - lo + 1) / 2;
+        if (off[m] <= k) lo = m;
+        else hi = m - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_budget_keys(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                                 unsigned long long n_nodes, const double* __restrict__ thr,
+                                                                 double* __restrict__ keys, unsigned* __restrict__ idx,
+                                                                 unsigned* __restrict__ row_of) {
+    const unsigned long long k = (unsigned long long)blockIdx.x * COARSEN_T + threadIdx.x;
+    if (k >= n_nodes) return;
+    const unsigned row = coarsen_row_of(off, n_rows, k);
+    const unsigned long long o0 = off[row], o1 = off[row + 1];
+    const bool interior = k > o0 && k + 1 < o1 && ((k - o0) & 1ull) == 0ull;
+    keys[k] = interior ? thr[k] : 0.0;
+    idx[k] = (unsigned)k;
+    row_of[k] = row;
+}
+
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_budget_rowkeys(const unsigned* __restrict__ row_of,
+                                                                    const unsigned* __restrict__ idx, unsigned long long n_nodes,
+                                                                    unsigned* __restrict__ keys) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * COARSEN_T + threadIdx.x;
+    if (j < n_nodes) keys[j] = row_of[min((unsigned long long)idx[j], n_nodes - 1)];
+}
+
+// One row per thread: the nodes of row i, sorted by (row, key), are [off[i], off[i + 1]) of idx.
+__global__ __launch_bounds__(COARSEN_T) void k_mesh_budget_pick(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                                 unsigned long long n_nodes, const double* __restrict__ thr,
+                                                                 const unsigned* __restrict__ idx, unsigned long long max_leaves,
+                                                                 double* __restrict__ eps) {
+    const unsigned i = blockIdx.x * COARSEN_T + threadIdx.x;
+    if (i >= n_rows) return;
+    const unsigned long long o0 = off[i], o1 = off[i + 1];
+    const unsigned long long L = o1 <= n_nodes ? coarsen_leaves(o0, o1) : 0u;
+    double e = -1.0;
+    if (L > max_leaves) e = thr[min((unsigned long long)idx[o1 - max_leaves], n_nodes - 1)];   // L - 1 >= max_leaves keys are thresholds
+    eps[i] = e;
+}
+
 // Gather n slots' totals into a caller device buffer as f64 [area, tasks, accepted, error] rows,
 // ready for one collective (counts are exact in f64 below 2^53). One thread per slot: the area is
 // the correctly rounded value of the slot's exact accumulator.
