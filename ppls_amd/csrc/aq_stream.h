@@ -33,6 +33,7 @@
 // tasks and accepted counts -- is bit-identical whatever the schedule.
 #pragma once
 #include "aq_device.h"
+#include "aq_ring_window.h"
 #include "aq_shape.h"
 #include "aq_xsum.h"
 
@@ -198,7 +199,21 @@ constexpr int CCAP = AQ_CCAP;
 #endif
 // the flush sums the lanes' area digits in an LDS window instead of a double-double wave reduction
 constexpr bool FLUSH_LDS = AQ_FLUSH_LDS;
-constexpr int REFILL = WCAP - 64;   // pairs a wave with an empty ring takes back from its cellar
+// The ring's lines (aq_ring_window.h: the rules and their invariants, walked state by state in
+// tests/test_ring_window.py). AQ_SPILL_LINE: a wave's pairs S = ring + held above which the ring's bottom
+// chunk goes to the cellar. The carried round never holds more than S (at its start) in the ring, so the
+// line is the ring's capacity; WCAP - 64 was the popped round's (r03), which put up to 128 pairs back
+// after taking 64 out. Bench launch, three interleaved passes on one box (profiles/ring_line/ab.json): 192
+// 79.59-79.77 ms (the parent, and this code at 192), 224 77.35-77.47, 256 75.85-76.04 ms (-4.7 %); HBM
+// writes per launch 38.7 -> 14.6 GB.
+#ifndef AQ_SPILL_LINE
+#define AQ_SPILL_LINE WCAP
+#endif
+#ifndef AQ_REFILL
+#define AQ_REFILL (WCAP - 64)
+#endif
+constexpr int REFILL = AQ_REFILL;   // pairs a wave with an empty ring takes back from its cellar, or from the
+                                    // pool (whole chunks into slots 0 .. REFILL - 1: <= the line, asserted below)
 #ifndef AQ_PF_BELOW
 // r02 A/B (8192-integral launch, GIVE_ROUNDS 32): 112 28.39, 96 27.93, 80 27.57, 64 27.20, 48 28.18,
 // 32 30.25 ms, no prefetch 33.37 ms. The old 128 (= WCAP - 128) made a ring that had just spilled
@@ -216,8 +231,16 @@ constexpr int PF_BELOW = AQ_PF_BELOW;   // below this ring size a wave prefetche
 #ifndef AQ_PF_ISSUE
 #define AQ_PF_ISSUE 160   // r03 A/B (8192 x eps=1e-10): 96 -0.6 %, 128 -1.8 %, 160 -2.4 % vs landing after one round
 #endif
+// (both lines were tuned against a spill line of 192 and hold at 256: the carried model, tools/ring_sim.py
+// --mode carried, moves only the cancels with the issue line, and the bench launch ran 75.85-76.04 ms at
+// 160 against 75.90-76.05 at 192; profiles/ring_line/ab.json)
 constexpr int PF_ISSUE = AQ_PF_ISSUE;
-static_assert(PF_ISSUE >= PF_BELOW && PF_BELOW + 64 <= WCAP - 64, "a landed prefetch must leave the ring below the spill line");
+constexpr RingLines RL{WCAP, AQ_SPILL_LINE, PF_ISSUE, PF_BELOW, REFILL};
+static_assert(ring_lines_valid(RL),
+              "ring lines: line <= WCAP, a landed prefetch stays at or below the line, a spill finds a whole chunk");
+static_assert(exit_chunks(RL, (unsigned)RL.line, 64u) <= 1u && max_exit_pairs(RL) - 64u <= (unsigned)WCAP,
+              "a burst's end moves out at most one chunk before it pushes the held pairs back");
+static_assert(WCAP / 2 <= PCAP && WCAP / 2 <= CH, "a give or a donation of half a full ring fits the pool / a chunk");
 // In-burst cellar moves (r03): a round that leaves the burst's size window at a cellar edge -- above
 // the spill line, or down to the prefetch issue / landing line -- moves the chunk inside the burst
 // and the burst goes on, where round 2 left the burst for the outer loop (~60 VALU and ~70 SALU of
@@ -239,8 +262,8 @@ static_assert(PF_ISSUE >= PF_BELOW && PF_BELOW + 64 <= WCAP - 64, "a landed pref
 // keeps the per-round test.)
 static_assert((AQ_MAX_LEVELS - 1) + (GIVE_ROUNDS > SKEWED_GIVE ? GIVE_ROUNDS : SKEWED_GIVE) < 256,
               "a burst's pairs past the depth cap must not carry the depth byte into the tag");
-constexpr int SPILL = 64;   // pairs a ring above WCAP - 64 moves to its cellar at once (r02 A/B: 128 at once
-                            // 4.0 % slower at eps 1e-10, 6.5 % at 1e-12: more refills)
+constexpr int SPILL = RING_CHUNK;   // pairs a wave above the spill line moves to its cellar at once (r02 A/B:
+                                    // 128 at once 4.0 % slower at eps 1e-10, 6.5 % at 1e-12: more refills)
 
 struct alignas(128) Line {
     unsigned v;
@@ -1028,6 +1051,49 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             }
         }
     };
+    // the ring's bottom chunk out of the wave: to its cellar, else the pool, else an HBM chunk (the outer
+    // loop's overflow path and a burst's end; bt / ct / pfn: the caller's ring bottom, cellar top and
+    // prefetch count). The ring holds >= 64 pairs above bt (aq_ring_window.h: spill, exit).
+    auto chunk_out = [&](unsigned& bt, unsigned& ct, unsigned& pfn) {
+        if (pfn) {
+            // a prefetch in flight is cancelled: its pairs never left the cellar (the loads land in
+            // registers nobody reads; the next spill writes above them)
+            ct += pfn;
+            pfn = 0;
+        }
+        if (ct + (unsigned)SPILL <= (unsigned)CCAP) {
+            spill_to_cellar(bt, ct);
+            ct += (unsigned)SPILL;
+            bt += (unsigned)SPILL;
+            return;
+        }
+        wave_lock(&S.lock, lane, lock_spins);
+        const unsigned pt = uni(S.ptop);
+        const bool fits = (pt - S.pbot) + 64u <= (unsigned)PCAP;
+        if (fits) {
+            copy_pair(R, base + ring_slot(bt + lane), POOL0 + ((pt + lane) & (PCAP - 1)));
+            if (lane == 0) S.ptop = pt + 64u;
+        }
+        wave_unlock(&S.lock, lane);
+        if (!fits) {
+            // pool full: spill 64 pairs to an HBM chunk (tokens first, then publish)
+            unsigned slot = 0;
+            if (lane == 0) {
+                slot = g_add(&qc->tail.v, 1u);
+                if (slot < P.qcap) g_add((int*)&qc->tokens.v, 64 + 1);   // records + 1 per chunk
+                spilled += 64;
+            }
+            slot = uni(__shfl(slot, 0, 64));
+            if (slot < P.qcap) {
+                const unsigned b = bt;
+                publish_chunk(P, R, slot, 64u, [&](unsigned i) { return base + ring_slot(b + i); }, lane);
+            } else {
+                err |= ERRB_OVERFLOW;   // pairs dropped: result invalid, error reported
+            }
+        }
+        if constexpr (DIAG) { if (lane == 0) atomicAdd(&s_dg[DG_POOL_PUSH], 64ull); }
+        bt += 64;
+    };
     const ExpConsts kk = pinned_exp_consts();
     // the depth cap per burst (see the file's configuration notes); the histogram instance keeps the
     // per-round test
@@ -1776,46 +1842,8 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
 
         // ---- keep the ring from overflowing: its bottom 64 pairs go to the cellar, else the pool,
         //      else an HBM chunk
-        if (size > (unsigned)(WCAP - 64)) {
-            if (pf_n) {
-                // a prefetch in flight is cancelled: its pairs never left the cellar (the loads land in
-                // registers nobody reads; the next spill writes above them)
-                ctop += pf_n;
-                pf_n = 0;
-            }
-            if (ctop + (unsigned)SPILL <= (unsigned)CCAP) {
-                spill_to_cellar(bot, ctop);
-                ctop += (unsigned)SPILL;
-                bot += (unsigned)SPILL;
-                __builtin_amdgcn_wave_barrier();
-                continue;
-            }
-            wave_lock(&S.lock, lane, lock_spins);
-            const unsigned pt = uni(S.ptop);
-            const bool fits = (pt - S.pbot) + 64u <= (unsigned)PCAP;
-            if (fits) {
-                copy_pair(R, base + ring_slot(bot + lane), POOL0 + ((pt + lane) & (PCAP - 1)));
-                if (lane == 0) S.ptop = pt + 64u;
-            }
-            wave_unlock(&S.lock, lane);
-            if (!fits) {
-                // pool full: spill 64 pairs to an HBM chunk (tokens first, then publish)
-                unsigned slot = 0;
-                if (lane == 0) {
-                    slot = g_add(&qc->tail.v, 1u);
-                    if (slot < P.qcap) g_add((int*)&qc->tokens.v, 64 + 1);   // records + 1 per chunk
-                    spilled += 64;
-                }
-                slot = uni(__shfl(slot, 0, 64));
-                if (slot < P.qcap) {
-                    const unsigned b = bot;
-                    publish_chunk(P, R, slot, 64u, [&](unsigned i) { return base + ring_slot(b + i); }, lane);
-                } else {
-                    err |= ERRB_OVERFLOW;   // pairs dropped: result invalid, error reported
-                }
-            }
-            if constexpr (DIAG) { if (lane == 0) atomicAdd(&s_dg[DG_POOL_PUSH], 64ull); }
-            bot += 64;
+        if (above_line(RL, size)) {
+            chunk_out(bot, ctop, pf_n);
             __builtin_amdgcn_wave_barrier();
             continue;
         }
@@ -1931,15 +1959,16 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
         // ds_read_b64 (12 array cycles) rather than three ds_read2st64_b64 (24). The window, the cellar lines and the accounting
         // count S = ring + held pairs; a burst starts with every pair in the ring and ends by pushing
         // the held ones back on top. Capacity: a round moves at most one pair per active lane into the
-        // ring, so the ring never holds more than S at a round's start; S <= WCAP - 64 then leaves
-        // room for the round (S grows by <= 64) and the final push.
+        // ring, so the ring never holds more than S at a round's start: rounds run up to S = the spill
+        // line <= WCAP. A burst can end up to 64 pairs above the line; its end then moves the ring's
+        // bottom chunk out before the final push (aq_ring_window.h).
         unsigned b_S = b_size, b_S0 = b_size;   // ring + held; the accounting base (moves with the cellar)
         unsigned long long b_am = 0;
         double ca = 0.0, cb = 0.0, cfa = 0.0, cfm = 0.0, cfb = 0.0, cdw = 0.0;   // the held pair (cdw: the dt word)
         unsigned b_lo1, b_span;
         auto window = [&]() {
-            b_lo1 = (b_pf != 0u ? (unsigned)PF_BELOW : (b_ctop > 0u ? (unsigned)PF_ISSUE : 0u)) + 1u;
-            b_span = (unsigned)(WCAP - 64) + 1u - b_lo1;
+            b_lo1 = burst_lo1(RL, b_pf != 0u, b_ctop > 0u);
+            b_span = burst_span(RL, b_lo1);
         };
         window();
         constexpr bool prio_by_load = PCU && FID == F_SIN_RECIP;
@@ -2043,14 +2072,15 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
             asm volatile("" : "+s"(b_re));
             const unsigned sz = b_S;
             if (b_re != 0u && sz != 0u) {
-                // a cellar edge: S > WCAP - 64 leaves >= WCAP - 128 >= SPILL pairs in the ring; S <=
-                // PF_BELOW leaves the ring room for the landing
-                if (sz > (unsigned)(WCAP - 64)) {
+                // a cellar edge: S above the line leaves >= line + 1 - 64 >= SPILL pairs in the ring; S <=
+                // PF_BELOW leaves the ring room for the landing (aq_ring_window.h)
+                if (above_line(RL, sz)) {
+                    // (a prefetch in flight is cancelled before the room test: its chunk is still the cellar's)
+                    if (b_pf) {
+                        b_ctop += b_pf;
+                        b_pf = 0;
+                    }
                     if (b_ctop + (unsigned)SPILL <= (unsigned)CCAP) {
-                        if (b_pf) {
-                            b_ctop += b_pf;
-                            b_pf = 0;
-                        }
                         spill_to_cellar(b_bot, b_ctop);
                         b_ctop += (unsigned)SPILL;
                         b_bot += (unsigned)SPILL;
@@ -2084,6 +2114,19 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
         // (a heavy burst ran at priority 3: back to 0 before the push-back, the outer loop, the locks and
         // the leader's polls -- ADVICE r4)
         if constexpr (prio_by_load) asm volatile("s_setprio 0");
+        // the per-burst depth cap: a pushed pair at depth >= max_depth means a task at the cap refined.
+        // Tested before anything leaves the wave (below)
+        bool b_capped = false;
+        if constexpr (burst_cap) b_capped = __ballot((acc.maxdt & 255u) >= (unsigned)max_depth) != 0ull;
+        // a burst that ended above the line: the ring's bottom chunk moves out (as in the outer loop: cellar,
+        // else pool, else HBM chunk) until the held pairs fit on top. At most one chunk (static_assert at
+        // RL); a capped burst's pairs are dropped below instead, its push may wrap over its own bottom
+        if (!__builtin_expect(b_capped, 0)) {
+            for (unsigned n = uni(exit_chunks(RL, b_top - b_bot, (unsigned)__popcll(b_am))); n != 0u; --n) {
+                chunk_out(b_bot, b_ctop, b_pf);
+                b_S0 -= 64u;
+            }
+        }
         // the held pairs back on top of the ring
         lds_push6_masked(b_am, ring_addr(ring8, ring_slot(b_top) + mbcnt(b_am), ring_vmask), ca, cb, cfa, cfm, cfb,
                          cdw);
@@ -2103,10 +2146,10 @@ __global__ __launch_bounds__(NWT * 64) void k_stream(StreamParams P) {
         acc.r = 0.0;
         if (b_dv) err |= ERRB_DEPTH;
         if constexpr (burst_cap) {
-            // the per-burst depth cap: a pushed pair at depth >= max_depth means a task at the cap
-            // refined. The wave drops its ring and cellar (the run is invalid) before anything can hand
-            // the pairs on, so nothing past the cap leaves the wave (the configuration notes above)
-            if (__builtin_expect(__ballot((acc.maxdt & 255u) >= (unsigned)max_depth) != 0ull, 0)) {
+            // the depth cap was exceeded: the wave drops its ring and cellar (the run is invalid) before
+            // anything can hand the pairs on, so nothing past the cap leaves the wave (the configuration
+            // notes above)
+            if (__builtin_expect(b_capped, 0)) {
                 err |= ERRB_DEPTH;
                 top = bot;
                 ctop = 0;
