@@ -670,6 +670,53 @@ int aq_mesh_coarsen_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, cons
                           const uint8_t *d_level, const double *d_thr, const double *d_eps, double eps,
                           const aq_mesh_batch_io *out, uint64_t cap_nodes, aq_mesh_coarsen_info *info);
 
+/* ---- mesh moments: per row the integral of (x - c)^k F over any sub-range, from the mesh ----------------
+ * M_k(i) = the integral over [lo_i, hi_i] of (x - c_i)^k fhat_i(x) dx, k = 0 .. order, where fhat_i is the
+ * piecewise-linear function through row i's nodes (d_offsets [n + 1], d_x, d_f; cum and level are not read) -- the
+ * function whose integral aq_mesh_eval returns. No evaluation of F: one pass over x and f. d_center, d_lo and d_hi
+ * are DEVICE [n] or NULL (c_i = 0.0, lo_i = the row's x_0, hi_i = the row's x_m); d_out is DEVICE [n * (order + 1)],
+ * row-major: M_0 .. M_order of row i.
+ * The term of one panel with ends x0 < x1 and values g0, g1 (after clipping, below), every line one IEEE double
+ * operation in this order (the library is built with -ffp-contract=off):
+ *     u0 = x0 - c;  u1 = x1 - c;  w = x1 - x0;
+ *     p0[0] = p1[0] = 1;  p0[i] = p0[i-1] * u0;  p1[i] = p1[i-1] * u1;
+ *     s0 = s1 = 0.0;  for j = 0 .. k in increasing order:
+ *         a = p0[k-j] * p1[j];  s0 = s0 + (double)(k+1-j) * a;  s1 = s1 + (double)(j+1) * a;
+ *     t_k = (g0 * s0 + g1 * s1) * w / (double)((k+1)*(k+2));      (a true division)
+ * For k = 0 this is (g0 + g1) * w / 2, the reference's larea and rarea (:189-190). The closed form is exact for a
+ * linear g; the computed t_k lies within (3k + 8) * 2^-53 * T_k of it to first order, T_k = w (|g0| + |g1|)
+ * max(|u0|, |u1|)^k / 2 (DESIGN 2.14 derives it).
+ * Range. A row's range is valid when x_0 <= lo_i <= hi_i <= x_m. An invalid range (NaN included) or a row of fewer
+ * than 3 nodes writes NaN to all order + 1 outputs of that row and disturbs no other row. lo_i == hi_i writes +0.0 to
+ * all of them and touches no panel (a zero-width row such as [1, 1] is safe). Otherwise the panel that holds q (lo or
+ * hi) is aq_mesh_eval's: the largest k <= m - 1 with x_k <= q, and the value there is aq_mesh_eval's expression
+ * fq = f_k + (f_k+1 - f_k) * ((q - x_k) / (x_k+1 - x_k)), always from the full panel's two nodes; a q equal to a node
+ * takes that node's stored f (hi at node x_k, k < m, ends the panel before it: no zero-width panel is added). A panel
+ * wholly inside the range is never interpolated, panels outside contribute nothing, and lo and hi in one panel give
+ * one clipped panel with both ends interpolated.
+ * Sum. Each M_k is carried in double-double and rounded once: before that rounding it lies within P_i * 2^-100 *
+ * sum |t_k| of the exact sum of the terms, P_i the panels in range. No float atomics: the reduction's shape depends
+ * on the row's own panel count and on the indices of the panels that hold lo_i and hi_i, on nothing else, so a row's
+ * outputs are bit-identical from run to run, in any batch, at any offset; and the outputs of an order = K call are,
+ * bit for bit, the first K + 1 outputs of an order = 4 call.
+ * The call only enqueues on the context's stream and reads nothing on the host; the inputs are not validated (every
+ * index a kernel forms stays inside its row's slice). AQ_EINVAL: a NULL ctx; order outside 0 .. AQ_MESH_MAX_MOMENT
+ * (whatever n); a NULL d_offsets, d_x, d_f or d_out with n > 0; an n that aq_mesh_err_batch refuses (n * 8 >= 2^31).
+ * n == 0: AQ_OK, nothing enqueued.
+ * Device memory. The block partials (8 * (order + 1) * 16 bytes per row) are context-owned and apart from
+ * aq_mesh_err_batch's, so the two calls may follow each other without waiting; allocated by the first call and grown
+ * on demand: aq_ctx_device_bytes does not move before that call, nor at a second call of the same n and order.
+ * Not covered: orders above 4; weights other than powers; meshes from the persistent kernel; shards and groups; the
+ * CLI; a single-mesh form (a batch of one row serves); a better deal of blocks for batches of few huge rows (eight
+ * workgroups per row whatever its size, as aq_mesh_err_batch). */
+#define AQ_MESH_MAX_MOMENT 4
+int aq_mesh_moments_batch(aq_ctx *ctx, size_t n, const uint64_t *d_offsets, const double *d_x, const double *d_f,
+                          int order,                   /* K, 0 .. AQ_MESH_MAX_MOMENT */
+                          const double *d_center,      /* DEVICE [n] or NULL: c_i (NULL: 0.0) */
+                          const double *d_lo,          /* DEVICE [n] or NULL: lo_i (NULL: the row's x_0) */
+                          const double *d_hi,          /* DEVICE [n] or NULL: hi_i (NULL: the row's x_m) */
+                          double *d_out);              /* DEVICE [n * (K + 1)] row-major: M_0 .. M_K of row i */
+
 /* ---- measurement ----------------------------------------------------------------------------
  * When enabled, HIP events bracket every launch of the persistent kernel, and of aq_mesh_invert's kernel, on
  * the context's stream; aq_kernel_time returns the summed milliseconds and launch count since the last reset. */

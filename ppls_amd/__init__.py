@@ -15,6 +15,7 @@ from .aquad import (  # noqa: F401
     DeviceBatch,
     Group,
     MeshBatch,
+    MeshStats,
     MeshTol,
     Problem,
     Result,
@@ -28,6 +29,6 @@ from .aquad import (  # noqa: F401
     user_integrand_name,
 )
 
-__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "DeviceBatch", "Group", "MeshBatch", "MeshTol", "Problem", "Result", "TolResult",
+__all__ = ["COSH4", "PARAM", "SIN_RECIP", "USER", "AquadError", "Context", "DeviceBatch", "Group", "MeshBatch", "MeshStats", "MeshTol", "Problem", "Result", "TolResult",
            "exact_round",
            "farmer", "format_reference", "integrate", "param_count", "param_integrand_name", "user_integrand_name"]

@@ -29,6 +29,7 @@ EXPORTS = (
     "aq_integrate_mesh_batch", "aq_mesh_eval_batch", "aq_mesh_invert_batch",
     "aq_mesh_refine_batch", "aq_mesh_err_batch",
     "aq_mesh_thresholds_batch", "aq_mesh_budget_batch", "aq_mesh_coarsen_batch",
+    "aq_mesh_moments_batch",
 )
 
 AQ_MAX_LEVELS = 128
@@ -38,6 +39,7 @@ AQ_EXACT_ROW = AQ_XS_LIMBS + 4
 AQ_GROUP_ID_BYTES = 128
 AQ_MAX_PARAMS = 4
 AQ_ENOCONV = -10
+AQ_MESH_MAX_MOMENT = 4
 
 
 class aq_problem(ctypes.Structure):
@@ -201,6 +203,7 @@ def load(build_if_missing=True):
         "aq_mesh_budget_batch": ([vp, ctypes.c_size_t, vp, vp, ctypes.c_uint64, vp], c_int),
         "aq_mesh_coarsen_batch": ([vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, c_dbl, ctypes.POINTER(aq_mesh_batch_io),
                                    ctypes.c_uint64, ctypes.POINTER(aq_mesh_coarsen_info)], c_int),
+        "aq_mesh_moments_batch": ([vp, ctypes.c_size_t, vp, vp, vp, c_int, vp, vp, vp, vp], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

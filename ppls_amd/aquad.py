@@ -91,6 +91,9 @@ ROW_TIMEOUT, ROW_OVERFLOW, ROW_DEPTH, ROW_INVALID = 1, 2, 4, 8   # aquad.h AQ_RO
 # (int32) as torch CUDA tensors of n; converged (bool: every row met its tolerance); evaluated (the task steps of
 # all rounds together = the tasks of the final trees).
 MeshTol = collections.namedtuple("MeshTol", "mesh err_abs err_signed eps_used rounds converged evaluated")
+# Context.mesh_stats's result: float64 CUDA tensors of n -- the integral of the row's density over the range, and the
+# mean, variance, skewness and kurtosis of the density normalised over it.
+MeshStats = collections.namedtuple("MeshStats", "mass mean var skew kurt")
 
 
 class MeshBatch:
@@ -797,6 +800,77 @@ class Context:
                                         err_abs.data_ptr(), err_signed.data_ptr()), "aq_mesh_err_batch")
         self.synchronize()
         return err_abs, err_signed
+
+    # -- mesh moments: the integral of (x - c)^k F over any sub-range, from the mesh ------------
+    def mesh_moments(self, mesh: MeshBatch, order=2, center=None, lo=None, hi=None):
+        """M_0 .. M_order of every row of a MeshBatch (aq_mesh_moments_batch): out[i, k] is the integral over
+        [lo_i, hi_i] of (x - c_i)^k times the piecewise-linear function through row i's nodes -- a float64 CUDA tensor
+        (n, order + 1). center, lo, hi: None (0.0, the row's first x, the row's last x), a float for every row, or a
+        float64 CUDA tensor (n,). A row without nodes or with a range outside x_0 <= lo <= hi <= x_m (NaN included) is
+        NaN; lo == hi gives +0.0. Bit-identical from run to run and in whatever batch a row sits."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n, order = len(mesh), int(order)
+        if not 0 <= order <= _lib.AQ_MESH_MAX_MOMENT:
+            raise ValueError(f"order must be in 0 .. {_lib.AQ_MESH_MAX_MOMENT}")
+        for t, what, dt in ((mesh.offsets, "mesh.offsets", torch.int64), (mesh.x, "mesh.x", torch.float64),
+                            (mesh.f, "mesh.f", torch.float64)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dt} tensor on {dev}")
+
+        def per_row(v, what):
+            if v is None:
+                return None
+            if isinstance(v, torch.Tensor):
+                if not (v.is_cuda and v.device == dev and v.dtype == torch.float64 and v.is_contiguous() and
+                        tuple(v.shape) == (n,)):
+                    raise ValueError(f"{what} must be None, a float, or a contiguous float64 tensor of shape ({n},) on {dev}")
+                return v
+            return torch.full((n,), float(v), dtype=torch.float64, device=dev)
+
+        center, lo, hi = per_row(center, "center"), per_row(lo, "lo"), per_row(hi, "hi")
+        out = torch.empty((n, order + 1), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        _check(self.L.aq_mesh_moments_batch(self._h, n, mesh.offsets.data_ptr(), mesh.x.data_ptr(), mesh.f.data_ptr(),
+                                            order, ptr(center), ptr(lo), ptr(hi), out.data_ptr()), "aq_mesh_moments_batch")
+        self.synchronize()
+        return out
+
+    def mesh_stats(self, mesh: MeshBatch, lo=None, hi=None) -> "MeshStats":
+        """(mass, mean, var, skew, kurt) of every row's density over [lo, hi], (n,) float64 CUDA tensors, from two
+        mesh_moments calls: order 1 about 0 gives c = M_1 / M_0; order 4 about c gives m_k = M_k / M_0 and d = m_1, and
+            mass = M_0, mean = c + d, var = m_2 - d d, mu3 = m_3 - 3 d m_2 + 2 d d d,
+            mu4 = m_4 - 4 d m_3 + 6 d d m_2 - 3 d d d d, skew = mu3 / (var sqrt(var)), kurt = mu4 / (var var),
+        each product and sum one float64 operation on the device, left to right. A row without nodes, an invalid range
+        or a mass of 0 gives NaN (mass itself is then NaN, NaN or 0)."""
+        import torch
+        first = self.mesh_moments(mesh, 1, None, lo, hi)
+        c = (first[:, 1] / first[:, 0]).contiguous()
+        M = self.mesh_moments(mesh, 4, c, lo, hi)
+        mass = M[:, 0].clone()
+        m1, m2, m3, m4 = (M[:, k] / mass for k in range(1, 5))
+        d = m1
+        mean = c + d
+        var = m2 - d * d
+        mu3 = m3 - 3.0 * d * m2 + 2.0 * d * d * d
+        mu4 = m4 - 4.0 * d * m3 + 6.0 * d * d * m2 - 3.0 * d * d * d * d
+        skew = mu3 / (var * torch.sqrt(var))
+        kurt = mu4 / (var * var)
+        return MeshStats(mass, mean, var, skew, kurt)
+
+    def mesh_tail_mean(self, mesh: MeshBatch, u, upper=False):
+        """E[X | X <= q] (upper: E[X | X >= q]) of every row's density at q = mesh_quantiles(mesh, u): M_1 / M_0 over
+        [x_0, q] (upper: [q, x_m]), one mesh_moments call per column of u. u: (nq,) or (n, nq) in [0, 1]; returns
+        (n, nq)."""
+        import torch
+        q = self.mesh_quantiles(mesh, u)
+        out = torch.empty_like(q)
+        for j in range(q.shape[1]):
+            qj = q[:, j].contiguous()
+            M = self.mesh_moments(mesh, 1, None, qj if upper else None, None if upper else qj)
+            out[:, j] = M[:, 1] / M[:, 0]
+        return out
 
     # -- mesh coarsening: any coarser mesh, or a leaf budget, from a fine mesh ------------------
     def _coarsen_inputs(self, mesh):

@@ -287,6 +287,7 @@ struct MeshBufs {
     PinBuf<unsigned> h_rtab;                       // pinned copy
     PinBuf<unsigned long long> h_rnodes;           // pinned: the input's node count (one word)
     DevBuf<double4> d_eparts{bytes};               // aq_mesh_err_batch's block partials (its first call)
+    DevBuf<double2> d_momparts{bytes};             // aq_mesh_moments_batch's block partials (its first call)
     // mesh coarsening (aq_mesh_thresholds_batch, aq_mesh_budget_batch, aq_mesh_coarsen_batch)
     DevBuf<ulonglong2> d_cpos{bytes};              // a leaf's 128-bit position, at slot (its first node) >> 1
     DevBuf<unsigned> d_crow{bytes};                // ... its row (0xffffffff: no leaf's slot)
@@ -2673,6 +2674,31 @@ int aq_mesh_err_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const do
     hipLaunchKernelGGL(k_mesh_err_finish, dim3((unsigned)((n + MESH_T - 1) / MESH_T)), dim3(MESH_T), 0, ctx->stream,
                        (const unsigned long long*)d_offsets, (unsigned)n, (const double4*)ctx->mesh.d_eparts.get(), d_err_abs,
                        d_err_signed);
+    AQ_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+// M_0 .. M_order of every row of a batch mesh over the row's range (aquad.hip k_mesh_moments_*). Only enqueues.
+int aq_mesh_moments_batch(aq_ctx* ctx, size_t n, const uint64_t* d_offsets, const double* d_x, const double* d_f,
+                          int order, const double* d_center, const double* d_lo, const double* d_hi, double* d_out) {
+    static_assert(AQ_MESH_MAX_MOMENT == 4, "one instance of k_mesh_moments_parts per order");
+    if (!ctx) return AQ_EINVAL;
+    if (order < 0 || order > AQ_MESH_MAX_MOMENT) return AQ_EINVAL;
+    if (n > 0 && (!d_offsets || !d_x || !d_f || !d_out)) return AQ_EINVAL;
+    if (n == 0) return AQ_OK;
+    if (n > 0x7fffffffull / MESH_MOM_B) return AQ_EINVAL;
+    AQ_HIP(hipSetDevice(ctx->device));
+    AQ_HIP(ctx->mesh.d_momparts.grow(n * MESH_MOM_B * (size_t)(order + 1)));
+    using Parts = void (*)(const unsigned long long*, const double*, const double*, const double*, const double*,
+                           const double*, double2*);
+    static const Parts parts[AQ_MESH_MAX_MOMENT + 1] = {k_mesh_moments_parts<0>, k_mesh_moments_parts<1>, k_mesh_moments_parts<2>,
+                                                        k_mesh_moments_parts<3>, k_mesh_moments_parts<4>};
+    hipLaunchKernelGGL(parts[order], dim3((unsigned)(n * MESH_MOM_B)), dim3(MESH_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, d_x, d_f, d_center, d_lo, d_hi, ctx->mesh.d_momparts.get());
+    AQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_moments_finish, dim3((unsigned)((n + MESH_T - 1) / MESH_T)), dim3(MESH_T), 0, ctx->stream,
+                       (const unsigned long long*)d_offsets, (unsigned)n, d_x, order, d_lo, d_hi,
+                       (const double2*)ctx->mesh.d_momparts.get(), d_out);
     AQ_HIP(hipGetLastError());
     return AQ_OK;
 }

@@ -1569,6 +1569,196 @@ __global__ __launch_bounds__(MESH_T) void k_mesh_err_finish(const unsigned long 
     if (err_signed) err_signed[i] = none ? nan : SH + SL;
 }
 
+// aq_mesh_moments_batch: per row M_k = the integral over [lo, hi] of (x - c)^k times the piecewise-linear function
+// through the row's nodes, k = 0 .. K, every panel's term the sequence include/aquad.h states (one IEEE operation
+// per line), carried in double-double. The arrangement is k_mesh_err_*'s: block (i, b) of MESH_MOM_B takes the row's
+// chunks of MESH_T leaves b, b + MESH_MOM_B, ... from the ROW's first leaf, skipping the chunks before the leaf that
+// holds lo and after the one that holds hi; a thread adds the two panels of its leaf in order, the wave's lanes
+// meet in a butterfly, the waves in order, and k_mesh_moments_finish adds a row's partials in block order and
+// rounds once. The shape depends on the row's leaf count and the two panel indices alone. The row's range is found
+// by ONE thread per block (two searches of the row's x, side by side) and handed to the others through LDS; a block
+// without a chunk in the range -- b * MESH_T >= the row's leaves, most blocks of a batch of small rows -- writes
+// (0, 0), the sum of no terms, and leaves before any search, barrier or butterfly.
+constexpr int MESH_MOM_B = 8;
+enum : int { MOM_NAN = 0, MOM_ZERO = 1, MOM_SUM = 2 };
+struct MomRange {
+    double c, lo, hi, flo, fhi;       // the centre, the range and the interpolant at an end inside a panel
+    unsigned long long kl, kh;        // the panels that hold lo and hi
+    int state;
+    bool lo_node, hi_node;            // the end is a node: its stored f
+};
+
+// what a row's outputs are: NaN (fewer than 3 nodes, or not x_0 <= lo <= hi <= x_m: NaN fails every comparison), +0.0
+// (lo == hi: no panel is touched), or a sum
+__device__ __forceinline__ int mesh_mom_state(double x0, double xm, double lo, double hi) {
+    if (!(x0 <= lo && lo <= hi && hi <= xm)) return MOM_NAN;
+    return lo == hi ? MOM_ZERO : MOM_SUM;
+}
+
+// one panel's terms t_0 .. t_K into the accumulators: include/aquad.h's sequence, line for line
+template <int K>
+__device__ __forceinline__ void mesh_mom_panel(double x0, double x1, double g0, double g1, double c, double (&ah)[K + 1],
+                                               double (&al)[K + 1]) {
+    const double u0 = x0 - c;
+    const double u1 = x1 - c;
+    const double w = x1 - x0;
+    double p0[K + 1], p1[K + 1];
+    p0[0] = 1.0;
+    p1[0] = 1.0;
+#pragma unroll
+    for (int i = 1; i <= K; ++i) {
+        p0[i] = p0[i - 1] * u0;
+        p1[i] = p1[i - 1] * u1;
+    }
+#pragma unroll
+    for (int k = 0; k <= K; ++k) {
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int j = 0; j <= k; ++j) {
+            const double a = p0[k - j] * p1[j];
+            s0 = s0 + (double)(k + 1 - j) * a;
+            s1 = s1 + (double)(j + 1) * a;
+        }
+        const double t = (g0 * s0 + g1 * s1) * w / (double)((k + 1) * (k + 2));
+        dd_add(ah[k], al[k], t);
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(MESH_T) void k_mesh_moments_parts(const unsigned long long* __restrict__ off,
+                                                               const double* __restrict__ x, const double* __restrict__ f,
+                                                               const double* __restrict__ center,
+                                                               const double* __restrict__ d_lo,
+                                                               const double* __restrict__ d_hi,
+                                                               double2* __restrict__ parts) {
+    __shared__ MomRange s_r;
+    __shared__ double s_v[MESH_NW][2 * (K + 1)];
+    const unsigned row = blockIdx.x / MESH_MOM_B, b = blockIdx.x % MESH_MOM_B;
+    const unsigned long long o0 = off[row], o1 = off[row + 1];
+    const unsigned long long nn = o1 > o0 ? o1 - o0 : 0ull, leaves = nn >= 3 ? (nn - 1) / 2 : 0ull;
+    const double* xr = x + o0;
+    const double* fr = f + o0;
+    // a block without a chunk (seven of eight on a row of at most MESH_T leaves) adds nothing: (0, 0), what the
+    // reduction of untouched accumulators gives, without the search, the barriers and the butterflies
+    if ((unsigned long long)b * MESH_T >= leaves) {
+        if ((int)threadIdx.x <= K) parts[(size_t)blockIdx.x * (K + 1) + threadIdx.x] = make_double2(0.0, 0.0);
+        return;
+    }
+    if (threadIdx.x == 0) {
+        // (nn >= 3 here: the block has a chunk.) Everything the classification reads, in one round trip; for the
+        // row's own ends -- the NULL arrays -- nothing more is loaded before the barrier.
+        const unsigned long long m = 2 * leaves;   // panels; the nodes past 2 * leaves (an even count) are not read
+        const double x0 = xr[0], xlast = xr[nn - 1], x1 = xr[1], xm1 = xr[m - 1], xm = xr[m];
+        const double lo = d_lo ? d_lo[row] : x0, hi = d_hi ? d_hi[row] : xlast;
+        s_r.c = center ? center[row] : 0.0;
+        const int state = mesh_mom_state(x0, xlast, lo, hi);
+        unsigned long long kl = 0, kh = 0;
+        bool lo_node = true, hi_node = true;
+        if (state == MOM_SUM) {
+            // aq_mesh_eval's rule for lo and hi -- the largest k <= m - 1 with x_k <= q, mesh_eval_one's search -- the
+            // two searches side by side (their loads overlap); x_1 > lo leaves panel 0 and x_(m-1) <= hi panel m - 1
+            // without a step. xkl, xkh: x at the two answers.
+            unsigned long long el = x1 > lo ? 0 : m - 1, eh = m - 1;
+            kh = xm1 <= hi ? m - 1 : 0;
+            double xkl = x0, xkh = kh ? xm1 : x0;
+            while (kl < el || kh < eh) {
+                const unsigned long long ml = kl + (el - kl + 1) / 2, mh = kh + (eh - kh + 1) / 2;
+                const double xl = xr[ml], xh = xr[mh];
+                if (kl < el) {
+                    if (xl <= lo) { kl = ml; xkl = xl; }
+                    else el = ml - 1;
+                }
+                if (kh < eh) {
+                    if (xh <= hi) { kh = mh; xkh = xh; }
+                    else eh = mh - 1;
+                }
+            }
+            if (kh > kl && hi == xkh) --kh;          // hi at a node: the panel that ends there, and the node's own f
+            else hi_node = kh == m - 1 && hi == xm;  // (else inside panel kh, or at the row's last node)
+            lo_node = lo == xkl;
+            if (!lo_node || !hi_node) {              // an end inside a panel: aq_mesh_eval's expression on its two nodes
+                const double xl = xr[kl], fl = fr[kl], xl1 = xr[kl + 1], fl1 = fr[kl + 1];
+                const double xh = xr[kh], fh = fr[kh], xh1 = xr[kh + 1], fh1 = fr[kh + 1];
+                s_r.flo = fl + (fl1 - fl) * ((lo - xl) / (xl1 - xl));
+                s_r.fhi = fh + (fh1 - fh) * ((hi - xh) / (xh1 - xh));
+            }
+        }
+        s_r.lo = lo;
+        s_r.hi = hi;
+        s_r.kl = kl;
+        s_r.kh = kh;
+        s_r.lo_node = lo_node;
+        s_r.hi_node = hi_node;
+        s_r.state = state;
+    }
+    __syncthreads();
+    const unsigned long long kl = s_r.kl, kh = s_r.kh;
+    // the first chunk at or after the one that holds leaf kl / 2, among b, b + MESH_MOM_B, ...
+    const unsigned long long c0 = (kl >> 1) / MESH_T;
+    const unsigned long long cb = c0 + (b + MESH_MOM_B - (unsigned)(c0 % MESH_MOM_B)) % MESH_MOM_B;
+    if (s_r.state != MOM_SUM || cb * MESH_T > (kh >> 1)) {   // a NaN or +0.0 row, or no chunk of this block in the range
+        if ((int)threadIdx.x <= K) parts[(size_t)blockIdx.x * (K + 1) + threadIdx.x] = make_double2(0.0, 0.0);
+        return;
+    }
+    double ah[K + 1], al[K + 1];
+#pragma unroll
+    for (int k = 0; k <= K; ++k) ah[k] = al[k] = 0.0;
+    {
+        const double c = s_r.c, lo = s_r.lo, hi = s_r.hi, flo = s_r.flo, fhi = s_r.fhi;
+        const bool lo_in = !s_r.lo_node, hi_in = !s_r.hi_node;   // an end inside its panel: the interpolated value
+        for (unsigned long long j = cb * MESH_T + threadIdx.x; j <= (kh >> 1); j += (unsigned long long)MESH_MOM_B * MESH_T) {
+            const double* xs = xr + 2 * j;   // kh <= 2 * leaves - 1: j < leaves
+            const double* fs = fr + 2 * j;
+            const double l = xs[0], mid = xs[1], r = xs[2], fl = fs[0], fmid = fs[1], fr2 = fs[2];
+            const unsigned long long p = 2 * j;
+            if (p >= kl && p <= kh)
+                mesh_mom_panel<K>(p == kl ? lo : l, p == kh ? hi : mid, p == kl && lo_in ? flo : fl,
+                                  p == kh && hi_in ? fhi : fmid, c, ah, al);
+            if (p + 1 >= kl && p + 1 <= kh)
+                mesh_mom_panel<K>(p + 1 == kl ? lo : mid, p + 1 == kh ? hi : r, p + 1 == kl && lo_in ? flo : fmid,
+                                  p + 1 == kh && hi_in ? fhi : fr2, c, ah, al);
+        }
+    }
+    const unsigned w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k <= K; ++k) {
+        wave_sum_dd(ah[k], al[k]);
+        if (lane_id() == 0) { s_v[w][2 * k] = ah[k]; s_v[w][2 * k + 1] = al[k]; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= K) {   // accumulator k's waves, in order
+        double H = 0.0, L = 0.0;
+        for (int v = 0; v < MESH_NW; ++v) dd_add_dd(H, L, s_v[v][2 * threadIdx.x], s_v[v][2 * threadIdx.x + 1]);
+        parts[(size_t)blockIdx.x * (K + 1) + threadIdx.x] = make_double2(H, L);
+    }
+}
+
+__global__ __launch_bounds__(MESH_T) void k_mesh_moments_finish(const unsigned long long* __restrict__ off, unsigned n_rows,
+                                                                const double* __restrict__ x, int K,
+                                                                const double* __restrict__ d_lo,
+                                                                const double* __restrict__ d_hi,
+                                                                const double2* __restrict__ parts, double* __restrict__ out) {
+    const unsigned i = blockIdx.x * MESH_T + threadIdx.x;
+    if (i >= n_rows) return;
+    const unsigned long long o0 = off[i], o1 = off[i + 1];
+    const unsigned long long nn = o1 > o0 ? o1 - o0 : 0ull;
+    int state = MOM_NAN;
+    if (nn >= 3) {
+        const double x0 = x[o0], xm = x[o0 + nn - 1];
+        state = mesh_mom_state(x0, xm, d_lo ? d_lo[i] : x0, d_hi ? d_hi[i] : xm);
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int k = 0; k <= K; ++k) {
+        double H = 0.0, L = 0.0;
+        if (state == MOM_SUM)
+            for (int b = 0; b < MESH_MOM_B; ++b) {
+                const double2 p = parts[((size_t)i * MESH_MOM_B + b) * (K + 1) + k];
+                dd_add_dd(H, L, p.x, p.y);
+            }
+        out[(size_t)i * (K + 1) + k] = state == MOM_NAN ? nan : state == MOM_ZERO ? 0.0 : H + L;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Mesh coarsening (aq_mesh_thresholds_batch, aq_mesh_budget_batch, aq_mesh_coarsen_batch): the converse of
 // refinement. The tree at eps' >= eps is a sub-tree of the tree at eps, and every value its tasks computed is a
